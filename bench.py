@@ -2,7 +2,13 @@
 """Headline benchmark: IQ frames/s of one full training step (forward + label-smoothed CE + backward +
 gradient all-reduce + clip + AdamW) on synthetic frames already resident in HBM.
 
-  python bench.py --gpus N --steps K --warmup W [--config B|C|Cp|D|A|ref] [--batch per-GPU]
+  python bench.py --gpus N --steps K --warmup W [--config B|C|Cp|D|A|ref] [--batch per-GPU] [--full]
+                  [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the result line; nothing else.  --full adds the legs below
+(each can still be left out with its --no-* option).  --dump-outputs DIR writes what the last timed step computed
+(logits, updated fp32 parameters, their gradients) and the result line's final_loss / train_acc as DIR/<name>.npy; inputs,
+initial weights and dropout streams are seeded, so two builds run with the same arguments can be compared output for output.
 
 N > 1 without a launcher: bench.py starts its own N ranks (one process per GPU, RCCL) BEFORE touching the GPU and
 exits non-zero unless all N joined.  Under `python -m torch.distributed.run ... bench.py --gpus N` it reads
@@ -10,7 +16,7 @@ RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment instead.
 
 Default workload = BASELINE.json configs[1]: ViT-Tiny/16 on 224x224 single-channel frames, 19 classes,
 256 frames per GPU, dropout 0.1 ON, bf16 activations / fp32 master weights.  Weak scaling: per-GPU batch fixed.
-Rank 0 prints ONE JSON line (contract in the task statement) with extra objects:
+Rank 0 prints ONE JSON line with extra objects (null in a plain run):
   roofline     -- dominant kernel family, timed live with HIP event pairs on the launch stream
                   (iq_prof_* in include/iqvit.h) over profiled steps of the same workload
   cpu_baseline -- the CPU oracle (oracle/iq_oracle.py, "port") timed on this host's cores on a bounded sample
@@ -54,6 +60,28 @@ MFMA_PEAK_TFLOPS = 2500.0    # dense bf16
 RIDGE = MFMA_PEAK_TFLOPS * 1e12 / (HBM_PEAK_GBS * 1e9)
 FAMILIES = ["gemm_nt", "wgrad", "attn_fwd", "attn_bwd", "ln_fwd", "ln_bwd", "misc", "optimizer"]
 PROFILE_ROUND = "r03"        # profiles/<round>_pmc_family_cfg<id>.json holds the PMC passes of this round's kernels
+DUMP_BYTES = 64 << 20        # --dump-outputs: at most this much in all
+DUMP_WHOLE = 1 << 20         # arrays up to this many elements are always written whole
+
+
+def dump_outputs(path, arrays):
+    """arrays: name -> numpy array (float32, or float64 scalars).  Arrays of more than DUMP_WHOLE elements share what the
+    small ones leave of DUMP_BYTES; when they do not fit, each is written as the same seeded sample of its flattened
+    elements (sorted indices), so runs with the same arguments stay comparable element for element."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    big = sum(v.nbytes for v in arrays.values() if v.size > DUMP_WHOLE)
+    room = DUMP_BYTES - sum(v.nbytes for v in arrays.values() if v.size <= DUMP_WHOLE) - 1024 * len(arrays)   # .npy headers
+    keep = 1.0 if big <= room else room / big
+    for name, v in arrays.items():
+        note = ""
+        if keep < 1.0 and v.size > DUMP_WHOLE:
+            m = int(v.size * keep)
+            idx = np.sort(np.random.default_rng(0).choice(v.size, m, replace=False, shuffle=False))
+            v = v.reshape(-1)[idx]
+            note = f" (seeded sample of {m} elements)"
+        np.save(os.path.join(path, name + ".npy"), v)
+        print(f"[bench] dump {name}: {v.dtype} {tuple(v.shape)}{note}", file=sys.stderr)
 
 
 def geometry(kind, kw):
@@ -268,9 +296,10 @@ def self_launch(a, argv):
     return 0
 
 
-def measure(a, config_id, dev, rank, world, steps, warmup, prof_steps, want_cpu):
-    """Timed steps + profiled leg (+ CPU baseline) for one named configuration -> dict of results (rank 0) or None."""
+def measure(a, config_id, dev, rank, world, steps, warmup, prof_steps, want_cpu, want_roofline, dump_dir=None):
+    """Timed steps (+ profiled leg, CPU baseline) for one named configuration -> dict of results (rank 0) or None."""
     import ctypes
+    import numpy as np
     import torch
     import torch.distributed as dist
     import vit_vs_raw_iq_amd as P
@@ -312,10 +341,15 @@ def measure(a, config_id, dev, rank, world, steps, warmup, prof_steps, want_cpu)
     loss, acc, _ = tr.read_stats()
     frames = B * world * steps
     value = frames / el
+    if dump_dir and rank == 0:
+        # before the profiled leg, whose extra steps would move the parameters on
+        dump_outputs(dump_dir, {"logits": tr._logits.cpu().numpy(), "params": tr.plan.flat.cpu().numpy(),
+                                "grads": tr.gflat.cpu().numpy(), "final_loss": np.array([loss], dtype=np.float64),
+                                "train_acc": np.array([acc], dtype=np.float64)})
 
     geo = geometry(kind, kw)
     roof = None
-    if world > 1 and not a.no_roofline:
+    if world > 1 and want_roofline:
         # every rank must take the same number of steps (each step all-reduces): the profiled leg runs everywhere,
         # only rank 0 times its kernels
         if rank != 0:
@@ -323,7 +357,7 @@ def measure(a, config_id, dev, rank, world, steps, warmup, prof_steps, want_cpu)
             for _ in range(1 + prof_steps):
                 tr.step(x, y)
             torch.cuda.synchronize()
-    if rank == 0 and not a.no_roofline:
+    if rank == 0 and want_roofline:
         # profiled leg: same workload, eager launches, HIP event pair around every kernel-family call
         L = N.lib()
         tr.use_graph = False
@@ -445,6 +479,12 @@ def main():
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch (default: the config's)")
     ap.add_argument("--graph", type=int, default=-1, help="hipGraph replay of the step (default: on)")
     ap.add_argument("--buckets", type=int, default=4)
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline leg, CPU baseline, raw-IQ secondary and accuracy reproduction (the --no-* options "
+                         "below leave single legs out); a plain run times the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's logits, parameters and gradients, and final_loss / train_acc, as "
+                         "DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip the raw-IQ (cfg C) measurement beside cfg B")
@@ -453,6 +493,8 @@ def main():
     ap.add_argument("--no-accuracy", action="store_true", help="skip the accuracy reproduction (cfg A ViT + raw-IQ test geometry, GPU vs CPU oracle)")
     ap.add_argument("--drop", type=float, default=-1.0, help="override the config's dropout probability (diagnostics)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and a.gpus > 1:
@@ -484,15 +526,16 @@ def main():
             dist.init_process_group(backend)
         assert dist.get_world_size() == world
 
-    main_res = measure(a, a.config, dev, rank, world, a.steps, a.warmup, a.prof_steps,
-                       want_cpu=(world == 1 and not a.no_cpu_baseline))
+    want_cpu = a.full and world == 1 and not a.no_cpu_baseline
+    want_roofline = a.full and not a.no_roofline
+    main_res = measure(a, a.config, dev, rank, world, a.steps, a.warmup, a.prof_steps, want_cpu, want_roofline,
+                       dump_dir=a.dump_outputs)
     second = None
-    if a.config == "B" and not a.no_secondary and a.batch == 0:
-        second = measure(a, "C", dev, rank, world, a.steps, a.warmup, a.prof_steps,
-                         want_cpu=(world == 1 and not a.no_cpu_baseline))
+    if a.full and a.config == "B" and not a.no_secondary and a.batch == 0:
+        second = measure(a, "C", dev, rank, world, a.steps, a.warmup, a.prof_steps, want_cpu, want_roofline)
 
     acc = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and not a.no_accuracy and a.config == "B" and a.batch == 0:
+    if rank == 0 and want_cpu and not a.no_accuracy and a.config == "B" and a.batch == 0:
         acc = accuracy_reproduction(dev)
 
     if rank == 0:

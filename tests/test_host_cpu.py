@@ -310,3 +310,29 @@ def test_chain_kernels_keep_scratch_out_of_their_chunk_loops_and_pad_their_inlin
         assert found >= 1, f"{name}: no MFMA loop found"
         loops += found
     assert kernels == 72 and loops >= kernels, (kernels, loops)      # 2 widths x 3 shapes x 2 dropout x 3 stage modes, fwd + bwd
+
+
+def test_bench_dump_outputs_keeps_its_budget_and_samples_the_same_elements(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: small arrays are written whole; large ones, when they would pass the byte budget, as one
+    seeded sample of their elements -- the same one in every run, so two builds compare element for element."""
+    import numpy as np
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BYTES", 64 << 10)
+    monkeypatch.setattr(bench, "DUMP_WHOLE", 1000)
+    rng = np.random.default_rng(3)
+    arrays = {"logits": rng.standard_normal((16, 19), dtype=np.float32), "params": rng.standard_normal(40000, dtype=np.float32),
+              "grads": rng.standard_normal(40000, dtype=np.float32), "final_loss": np.array([2.5])}
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    bench.dump_outputs(str(tmp_path / "b"), arrays)
+    total = 0
+    for name, v in arrays.items():
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == v.dtype and np.array_equal(a, b)
+        total += os.path.getsize(tmp_path / "a" / f"{name}.npy")
+        if v.size <= 1000:
+            assert np.array_equal(a, v)
+        else:
+            assert 0 < a.size < v.size and np.isin(a, v).all()
+    assert total <= 64 << 10
+    bench.dump_outputs(str(tmp_path / "c"), {"params": arrays["params"][:10000]})       # fits: written whole
+    assert np.array_equal(np.load(tmp_path / "c" / "params.npy"), arrays["params"][:10000])
