@@ -228,6 +228,17 @@ int iq_attn_fwd_masked(const void* qkv, void* out, float* lse, const uint8_t* ma
                        int H, int dh, iq_stream_t stream);
 int iq_attn_bwd_masked(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv,
                        const uint8_t* mask, long mask_hstride, int B, int S, int H, int dh, iq_stream_t stream);
+/* The attention matrix the reference forms and drops (V/models/layers/scale_dot_product_attention.py:25-39 returns `score`,
+ * V/models/layers/multi_head_attention.py:24 discards it, :30 "5. visualize attention map").
+ * P = softmax(q k^T / sqrt(dh)) of the packed qkv [B*S, 3*H*dh] bf16 (layout of iq_attn_fwd), recomputed with the
+ * log-sum-exp iq_attn_fwd wrote (fp32 [B, H, S], natural log).  No S x S buffer exists in the forward.
+ *   rows  0: every query row      -> out[b*out_bstride + ((h*S + q)*S + key)]
+ *         1: query row 0 (CLS)    -> out[b*out_bstride + h*S + key]
+ *         2: mean over query rows -> out[b*out_bstride + h*S + key]
+ *   heads 0: per head (h < H), 1: mean over heads (h = 0 only)                       fp32 out, no atomics
+ * Same (S, dh) set as iq_attn_supported.  Two calls give the same bits. */
+int iq_attn_probs(const void* qkv, const float* lse, float* out, long out_bstride, int B, int S, int H, int dh,
+                  int rows, int heads, iq_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * Embedding front end.  iq_patchify turns the fp32 input frame batch into the bf16 GEMM
@@ -338,6 +349,21 @@ int iq_model_backward(iq_model_t* m, const float* dlogits, const float* denc, in
  * iq_model_grad_range below); vit-vs-raw-iq_amd/trainer.py issues one asynchronous all-reduce per range. */
 /* flat-gradient range [*off, *off+*len) written by stages [stage_lo, stage_hi] (DDP buckets) */
 int iq_model_grad_range(const iq_model_t* m, int stage_hi, int stage_lo, size_t* off, size_t* len);
+/* Attention read-back after iq_model_forward(..., batch, workspace): layer `layer`'s attention probabilities from that forward
+ * (see iq_attn_probs for rows / heads / out) -- the per-layer `score` of ScaleDotProductAttention.forward
+ * (V/models/layers/scale_dot_product_attention.py:25-39) that MultiHeadAttention.forward drops
+ * (V/models/layers/multi_head_attention.py:24,30; the raw-IQ tree's layers are the same files).
+ * Refused (iq_model_last_error) when no forward has run, when the last forward ran in another workspace or with another
+ * batch, for a layer outside [0, n_layers), bad rows / heads, a too-small workspace or out_bstride.  A forward replayed from
+ * a captured graph is not seen by the host: run a forward through this call before reading back. */
+int iq_model_attention(iq_model_t* m, const void* workspace, size_t ws_bytes, int batch, int layer, int rows,
+                       int heads, float* out, long out_bstride, iq_stream_t stream);
+/* Attention rollout (Abnar & Zuidema 2020) of that forward, over the same per-layer matrices as above:
+ * r <- start; for l = L-1 .. 0: r <- r (alpha * mean_h P_l + (1-alpha) I).  start = e_0 (CLS) when the model has a CLS token
+ * (V/models/amc_transformer.py:29 reads x[:, 0]), else uniform 1/S (the mean pooling of R/models/transformer_rawIQ.py:91-93).
+ * out fp32 [B, S]; each row sums to 1.  0 <= alpha <= 1; same refusals as iq_model_attention. */
+int iq_model_attention_rollout(iq_model_t* m, const void* workspace, size_t ws_bytes, int batch, float alpha,
+                               float* out, iq_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * Measurement aid (bench.py roofline leg): when enabled, every entry point above brackets its

@@ -7,6 +7,7 @@ Import name: `vit_vs_raw_iq_amd` (the directory name contains hyphens; the repo-
   modules   -- the reference's nn.Module surface (AMCTransformer x2, Encoder x2, layer shells)
   trainer   -- fused native training step (CE + backward + clip + AdamW) and data-parallel driver
   data      -- seeded synthetic IQ frames (the reference ships no data)
+  attention_maps -- per-layer attention probabilities and attention rollout from the fused forward pass
   _native   -- ctypes binding of include/iqvit.h  (libiqvit.so; no fallback)
   ViT.models.amc_transformer / transformer_rawIQ.models.transformer_rawIQ
             -- import paths used by the reference's scripts (hyperparameter_tuning.py:19,37)
@@ -15,7 +16,9 @@ from .modules import (AMCTransformerViT, AMCTransformerRawIQ, EncoderViT, Encode
                       MultiHeadAttention, PositionwiseFeedForward, ScaleDotProductAttention, PatchEmbedding,
                       SequenceEmbedding, NativePlan)
 from ._native import IqError, LIB_PATH
+from .attention_maps import attention_maps, attention_rollout, rollout_to_input
 
 __all__ = ["AMCTransformerViT", "AMCTransformerRawIQ", "EncoderViT", "EncoderRawIQ", "EncoderLayer", "LayerNorm",
            "MultiHeadAttention", "PositionwiseFeedForward", "ScaleDotProductAttention", "PatchEmbedding",
-           "SequenceEmbedding", "NativePlan", "IqError", "LIB_PATH"]
+           "SequenceEmbedding", "NativePlan", "IqError", "LIB_PATH", "attention_maps", "attention_rollout",
+           "rollout_to_input"]

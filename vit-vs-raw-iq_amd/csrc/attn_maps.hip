@@ -1,0 +1,368 @@
+// Attention probabilities and attention rollout, read back from what a forward left in its workspace, for gfx950 (MI355X).
+//
+// Reference: MultiHeadAttention.forward receives the attention matrix from ScaleDotProductAttention and drops it
+// (V/models/layers/multi_head_attention.py:24,30, "5. visualize attention map"); scale_dot_product_attention.py:23-39 forms
+// it as softmax(q k^T / sqrt(dh)).  The fused forward (attention.hip) never writes that matrix.  It keeps the packed bf16
+// q|k|v and the fp32 log-sum-exp of every query row, and these kernels rebuild
+//   P[q, key] = exp2(q.k * log2(e)/sqrt(dh) - lse[q] * log2(e))
+// from them: the forward's products (mfma_f32_16x16x32_bf16, key tile as A, query tile as B, the same contraction slots) and
+// the backward's exponent argument (attention.hip, attn_bwd_kernel / attn_frame_bwd_kernel).
+//
+// Work unit: one head's 32-query block against a chunk of up to KC = 256 keys.  The Q block and the K chunk are staged in LDS;
+// wave w computes key tiles w and w + 8 (16 keys each) for both 16-query halves, so the lane of query c16 holds 4 consecutive
+// keys, which go to an fp32 LDS tile Pt[32][KC].  From there:
+//   rows 0, heads 0   the tile is copied out.  Its rows are consecutive in `out` (one contiguous range when the chunk is the
+//                     whole row): 16-byte stores from the first 16-byte boundary on, 4-byte stores at the two ragged ends
+//                     (S is odd wherever a CLS token precedes a power-of-two token count)
+//   rows 0, heads 1   the lanes sum their tiles over the heads in registers (h = 0 .. H-1), scale by 1/H, then as above
+//   rows 1, 2         thread `col` sums its key column of the tile (query 0 only, resp. every real query, in order)
+// No atomics: every output element is written by one thread of one workgroup and every sum runs in a fixed order, so two
+// calls give the same bits.
+#include <stdint.h>
+
+#include "attn_maps.h"
+#include "common.h"
+#include "iqvit.h"
+#include "prof.h"
+
+namespace {
+
+constexpr int PM_THREADS = 512;
+constexpr int PM_WAVES = PM_THREADS / 64;
+constexpr int QB = 32;                       // queries per block
+constexpr int KC = 256;                      // keys per chunk
+constexpr int KTW = KC / 16 / PM_WAVES;      // key tiles per wave
+constexpr int PLD = KC + 4;                  // fp32 row stride of the probability tile
+constexpr float LOG2E = 1.4426950408889634f;
+
+__device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
+
+template <int DH> struct PmCfg {
+  static constexpr int LD = (DH == 16) ? 16 : DH + 16;   // LDS row stride (elements), as attention.hip
+  static constexpr int KS = (DH + 31) / 32;              // 32-deep contraction steps
+  static constexpr int CPR = DH / 8;                     // 16 B chunks per row
+};
+
+template <int DH>
+__device__ __forceinline__ bf16x8 row_frag(const bf16* tile, int row, int s, int lane) {
+  const int d0 = s * 32 + 8 * (lane >> 4);
+  bf16x8 v = {};
+  if (DH >= 32 || d0 < DH) v = *reinterpret_cast<const bf16x8*>(tile + row * PmCfg<DH>::LD + d0);
+  return v;
+}
+
+// rows [r0, r0 + nrows) of a head slice (global row stride ldg) -> LDS image; rows >= S are zero
+template <int DH>
+__device__ __forceinline__ void stage(bf16* img, const bf16* base, long ldg, int r0, int nrows, int S, int tid) {
+  constexpr int CPR = PmCfg<DH>::CPR, LD = PmCfg<DH>::LD;
+  for (int id = tid; id < nrows * CPR; id += PM_THREADS) {
+    const int r = id / CPR, c = id - r * CPR;
+    bf16x8 v = {};
+    if (r0 + r < S) v = *reinterpret_cast<const bf16x8*>(base + (long)(r0 + r) * ldg + c * 8);
+    *reinterpret_cast<bf16x8*>(img + r * LD + c * 8) = v;
+  }
+}
+
+// P^T tiles of this wave: p[u][j] = key tile (wave + 8 j) x query half u.  Lane: query c16 of the half, keys 4g .. 4g+3 of the
+// tile.  lq[u]: the lane's query lse * log2(e).  Keys >= S give 0; tiles past the chunk are not computed.
+template <int DH>
+__device__ __forceinline__ void tile_probs(const bf16* Qs, const bf16* Ks, const float lq[2], bool u1, int kc, int k0, int S,
+                                           float scale_log2, int wave, int lane, f32x4 p[2][KTW]) {
+  constexpr int KS = PmCfg<DH>::KS;
+  const int c16 = lane & 15, g = lane >> 4;
+  bf16x8 qf[2][KS];
+#pragma unroll
+  for (int u = 0; u < 2; ++u)
+#pragma unroll
+    for (int s = 0; s < KS; ++s) qf[u][s] = row_frag<DH>(Qs, u * 16 + c16, s, lane);
+#pragma unroll
+  for (int j = 0; j < KTW; ++j) {
+    const int kt = wave + PM_WAVES * j;
+    p[0][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    p[1][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (kt * 16 >= kc) continue;                 // wave-uniform
+    bf16x8 kf[KS];
+#pragma unroll
+    for (int s = 0; s < KS; ++s) kf[s] = row_frag<DH>(Ks, kt * 16 + c16, s, lane);
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      if (u == 1 && !u1) continue;               // wave-uniform: the second half holds no query
+      f32x4 a = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int s = 0; s < KS; ++s) a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[s], qf[u][s], a, 0, 0, 0);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float pv = fast_exp2(a[r] * scale_log2 - lq[u]);
+        p[u][j][r] = k0 + kt * 16 + 4 * g + r < S ? pv : 0.f;
+      }
+    }
+  }
+}
+
+__device__ __forceinline__ void tile_to_lds(float* Pt, const f32x4 p[2][KTW], int kc, int wave, int lane) {
+  const int c16 = lane & 15, g = lane >> 4;
+#pragma unroll
+  for (int j = 0; j < KTW; ++j) {
+    const int kt = wave + PM_WAVES * j;
+    if (kt * 16 >= kc) continue;
+#pragma unroll
+    for (int u = 0; u < 2; ++u) *reinterpret_cast<f32x4*>(Pt + (u * 16 + c16) * PLD + kt * 16 + 4 * g) = p[u][j];
+  }
+}
+
+// dst[0 .. n) <- tile rows of kc elements read in order (element e = row e / kc, column e % kc); threads t of nt.
+// 16-byte stores from dst's first 16-byte boundary on, 4-byte stores for at most 3 elements at either end.
+__device__ __forceinline__ void flush_rows(float* dst, int n, int kc, const float* Pt, int t, int nt) {
+  const int lead = min((int)((0u - (unsigned)((uintptr_t)dst >> 2)) & 3u), n);
+  const int nq4 = (n - lead) >> 2;
+  if (t < lead) {
+    const int r = t / kc;
+    dst[t] = Pt[r * PLD + t - r * kc];
+  }
+  for (int i = t; i < nq4; i += nt) {
+    const int e = lead + 4 * i;
+    int r = e / kc, c = e - r * kc;
+    f32x4 v;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      v[j] = Pt[r * PLD + c];
+      if (++c == kc) { c = 0; ++r; }
+    }
+    *reinterpret_cast<f32x4*>(dst + e) = v;
+  }
+  const int e = lead + 4 * nq4 + t;
+  if (e < n) {
+    const int r = e / kc;
+    dst[e] = Pt[r * PLD + e - r * kc];
+  }
+}
+
+struct ProbsArgs {
+  const bf16* qkv;
+  const float* lse;
+  float* out;
+  long bstride;
+  int S, H, rows, heads;
+  int nhg, nqg;        // head groups / query-block groups per frame in the grid (1: the workgroup loops over all of them)
+  float scale_log2;
+};
+
+template <int DH>
+__global__ __launch_bounds__(PM_THREADS) void attn_probs_kernel(ProbsArgs a) {
+  using Cf = PmCfg<DH>;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  bf16* Qs = reinterpret_cast<bf16*>(smem);
+  bf16* Ks = Qs + QB * Cf::LD;
+  float* Pt = reinterpret_cast<float*>(Ks + KC * Cf::LD);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c16 = lane & 15;
+  const int S = a.S, H = a.H, D = H * DH;
+  const long ldg = 3L * D;
+  const int nqb = a.rows == 1 ? 1 : (S + QB - 1) / QB;
+  int wg = blockIdx.x;
+  const int qg = wg % a.nqg;
+  wg /= a.nqg;
+  const int hg = wg % a.nhg, b = wg / a.nhg;
+  const int h_lo = a.nhg == 1 ? 0 : hg, nh = a.nhg == 1 ? H : 1;
+  const int qb_lo = a.nqg == 1 ? 0 : qg, nq = a.nqg == 1 ? nqb : 1;
+  const bf16* fq = a.qkv + (long)b * S * ldg;
+  float* ob = a.out + (long)b * a.bstride;
+  const bool qouter = a.rows == 0;     // rows 0: heads innermost (their mean accumulates in registers); 1, 2: queries innermost
+  f32x4 acc[2][KTW];
+#pragma unroll
+  for (int j = 0; j < KTW; ++j) { acc[0][j] = f32x4{0.f, 0.f, 0.f, 0.f}; acc[1][j] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+  float csum = 0.f;
+  for (int k0 = 0; k0 < S; k0 += KC) {
+    const int kc = min(KC, S - k0);
+    for (int t = 0; t < nh * nq; ++t) {
+      const int hi = qouter ? t % nh : t / nq, qi = qouter ? t / nh : t % nq;
+      const int h = h_lo + hi, q0 = (qb_lo + qi) * QB;
+      const bf16* hq = fq + h * DH;
+      stage<DH>(Qs, hq, ldg, q0, QB, S, tid);
+      stage<DH>(Ks, hq + D, ldg, k0, (kc + 15) / 16 * 16, S, tid);
+      float lq[2];
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const int q = q0 + u * 16 + c16;
+        lq[u] = q < S ? a.lse[((long)b * H + h) * S + q] * LOG2E : 0.f;
+      }
+      __syncthreads();
+      f32x4 p[2][KTW];
+      tile_probs<DH>(Qs, Ks, lq, a.rows != 1 && q0 + 16 < S, kc, k0, S, a.scale_log2, wave, lane, p);
+      __syncthreads();                           // Qs / Ks free for the next item
+      const int nrow = a.rows == 1 ? 1 : min(QB, S - q0);
+      if (a.rows == 0 && a.heads == 1) {
+        const float inv = 1.0f / H;
+#pragma unroll
+        for (int j = 0; j < KTW; ++j)
+#pragma unroll
+          for (int u = 0; u < 2; ++u) acc[u][j] += p[u][j];
+        if (hi < nh - 1) continue;
+#pragma unroll
+        for (int j = 0; j < KTW; ++j)
+#pragma unroll
+          for (int u = 0; u < 2; ++u) { p[u][j] = acc[u][j] * inv; acc[u][j] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+      }
+      tile_to_lds(Pt, p, kc, wave, lane);
+      __syncthreads();
+      // (the next write of Pt follows the next item's two barriers)
+      if (a.rows == 0) {
+        float* dst = ob + ((long)(a.heads ? 0 : h) * S + q0) * S;
+        if (kc == S) flush_rows(dst, nrow * S, S, Pt, tid, PM_THREADS);
+        else
+          for (int r = wave; r < nrow; r += PM_WAVES) flush_rows(dst + (long)r * S + k0, kc, kc, Pt + r * PLD, lane, 64);
+      } else if (tid < kc) {
+        float s = 0.f;
+        for (int r = 0; r < nrow; ++r) s += Pt[r * PLD + tid];
+        csum += s;
+        if (a.heads ? t == nh * nq - 1 : qi == nq - 1) {
+          const float norm = (a.rows == 2 ? 1.0f / S : 1.0f) * (a.heads ? 1.0f / H : 1.0f);
+          ob[(long)(a.heads ? 0 : h) * S + k0 + tid] = csum * norm;
+          csum = 0.f;
+        }
+      }
+    }
+  }
+}
+
+// Rollout: one workgroup per frame, r and the next r in LDS.  Per layer (top down), chunk of keys, head and query block, the
+// P tile goes to LDS and thread `col` adds sum_q r[q] P[q, col] in order; the chunk's new r is
+// alpha * (that / H) + (1 - alpha) * r[col].
+struct RolloutArgs {
+  const unsigned char* qkv0;
+  long qkv_lstride;
+  const unsigned char* lse0;
+  long lse_lstride;
+  float* out;
+  int L, S, H, cls;
+  float alpha, scale_log2;
+};
+
+template <int DH>
+__global__ __launch_bounds__(PM_THREADS) void attn_rollout_kernel(RolloutArgs a) {
+  using Cf = PmCfg<DH>;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  bf16* Qs = reinterpret_cast<bf16*>(smem);
+  bf16* Ks = Qs + QB * Cf::LD;
+  float* Pt = reinterpret_cast<float*>(Ks + KC * Cf::LD);
+  const int S = a.S, H = a.H, D = H * DH;
+  const int spad = (S + QB - 1) / QB * QB;
+  float* r = Pt + QB * PLD;
+  float* rn = r + spad;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c16 = lane & 15;
+  const long ldg = 3L * D;
+  const int b = blockIdx.x, nqb = spad / QB;
+  for (int i = tid; i < spad; i += PM_THREADS) r[i] = i < S ? (a.cls ? (i == 0 ? 1.f : 0.f) : 1.0f / S) : 0.f;
+  __syncthreads();
+  for (int l = a.L - 1; l >= 0; --l) {
+    const bf16* fq = reinterpret_cast<const bf16*>(a.qkv0 + l * a.qkv_lstride) + (long)b * S * ldg;
+    const float* lse = reinterpret_cast<const float*>(a.lse0 + l * a.lse_lstride) + (long)b * H * S;
+    for (int k0 = 0; k0 < S; k0 += KC) {
+      const int kc = min(KC, S - k0);
+      float col = 0.f;
+      for (int t = 0; t < H * nqb; ++t) {
+        const int h = t / nqb, q0 = (t - h * nqb) * QB;
+        const bf16* hq = fq + h * DH;
+        stage<DH>(Qs, hq, ldg, q0, QB, S, tid);
+        stage<DH>(Ks, hq + D, ldg, k0, (kc + 15) / 16 * 16, S, tid);
+        float lq[2];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          const int q = q0 + u * 16 + c16;
+          lq[u] = q < S ? lse[(long)h * S + q] * LOG2E : 0.f;
+        }
+        __syncthreads();
+        f32x4 p[2][KTW];
+        tile_probs<DH>(Qs, Ks, lq, q0 + 16 < S, kc, k0, S, a.scale_log2, wave, lane, p);
+        __syncthreads();
+        tile_to_lds(Pt, p, kc, wave, lane);
+        __syncthreads();
+        if (tid < kc) {
+          const int nrow = min(QB, S - q0);
+          float s = 0.f;
+          for (int i = 0; i < nrow; ++i) s += r[q0 + i] * Pt[i * PLD + tid];
+          col += s;
+        }
+      }
+      if (tid < kc) rn[k0 + tid] = a.alpha * (col * (1.0f / H)) + (1.0f - a.alpha) * r[k0 + tid];
+    }
+    __syncthreads();
+    float* tmp = r;
+    r = rn;
+    rn = tmp;
+  }
+  for (int i = tid; i < S; i += PM_THREADS) a.out[(long)b * S + i] = r[i];
+}
+
+template <int DH> size_t probs_lds() { return (size_t)QB * PmCfg<DH>::LD * 2 + (size_t)KC * PmCfg<DH>::LD * 2 + (size_t)QB * PLD * 4; }
+
+template <int DH>
+int launch_probs(const ProbsArgs& a, int B, hipStream_t st) {
+  const size_t lds = probs_lds<DH>();
+  // per frame where the forward runs its per-frame kernel (short sequences); else per (frame, head, query block), with the
+  // groups a fixed-order mean needs kept inside one workgroup
+  const bool frame = a.S <= 128;
+  ProbsArgs g = a;
+  const int nqb = (a.S + QB - 1) / QB;
+  if (a.rows == 0) {
+    g.nhg = (a.heads == 1 || frame) ? 1 : a.H;
+    g.nqg = frame ? 1 : nqb;
+  } else {
+    g.nhg = (a.heads == 1 || frame) ? 1 : a.H;
+    g.nqg = 1;
+  }
+  (void)hipFuncSetAttribute((const void*)attn_probs_kernel<DH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  attn_probs_kernel<DH><<<(unsigned)((long)B * g.nhg * g.nqg), PM_THREADS, lds, st>>>(g);
+  return iq_launch_status();
+}
+
+template <int DH>
+int launch_rollout(const RolloutArgs& a, int B, hipStream_t st) {
+  const size_t lds = probs_lds<DH>() + (size_t)2 * ((a.S + QB - 1) / QB * QB) * 4;
+  (void)hipFuncSetAttribute((const void*)attn_rollout_kernel<DH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  attn_rollout_kernel<DH><<<B, PM_THREADS, lds, st>>>(a);
+  return iq_launch_status();
+}
+
+}  // namespace
+
+extern "C" int iq_attn_probs(const void* qkv, const float* lse, float* out, long out_bstride, int B, int S, int H, int dh,
+                             int rows, int heads, iq_stream_t stream) {
+  if (B < 0 || H <= 0 || rows < 0 || rows > 2 || heads < 0 || heads > 1) return IQ_ERR_ARG;
+  if (!iq_attn_supported(S, dh)) return IQ_ERR_UNSUPPORTED;
+  if (B == 0) return IQ_OK;
+  if (!qkv || !lse || !out || ((uintptr_t)qkv & 15) || ((uintptr_t)out & 3)) return IQ_ERR_ARG;
+  if (out_bstride < (long)(heads ? 1 : H) * S * (rows == 0 ? S : 1)) return IQ_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  IQ_PROF(IQ_FAM_MISC, st);
+  {
+    const double qrows = rows == 1 ? 1.0 : (double)S;
+    const double outb = 4.0 * B * (heads ? 1 : H) * (rows == 0 ? (double)S * S : (double)S);
+    IQ_PROF_K(2.0 * B * S * 2.0 * H * dh + 4.0 * B * H * S + outb, 2.0 * B * H * qrows * S * dh, "attn_probs_kernel<%d>", dh);
+  }
+  ProbsArgs a;
+  a.qkv = (const bf16*)qkv; a.lse = lse; a.out = out; a.bstride = out_bstride;
+  a.S = S; a.H = H; a.rows = rows; a.heads = heads; a.nhg = 1; a.nqg = 1;
+  a.scale_log2 = LOG2E / sqrtf((float)dh);
+  switch (dh) {
+    case 16: return launch_probs<16>(a, B, st);
+    case 32: return launch_probs<32>(a, B, st);
+    default: return launch_probs<64>(a, B, st);
+  }
+}
+
+int attn_rollout_launch(const unsigned char* qkv0, long qkv_lstride, const unsigned char* lse0, long lse_lstride, int L,
+                        float* out, int B, int S, int H, int dh, int cls, float alpha, hipStream_t st) {
+  if (B <= 0) return IQ_OK;
+  if (!iq_attn_supported(S, dh)) return IQ_ERR_UNSUPPORTED;
+  IQ_PROF(IQ_FAM_MISC, st);
+  IQ_PROF_K((double)L * (2.0 * B * S * 2.0 * H * dh + 4.0 * B * H * S) + 4.0 * B * S, 2.0 * L * B * H * (double)S * S * (dh + 1),
+            "attn_rollout_kernel<%d>", dh);
+  RolloutArgs a;
+  a.qkv0 = qkv0; a.qkv_lstride = qkv_lstride; a.lse0 = lse0; a.lse_lstride = lse_lstride; a.out = out;
+  a.L = L; a.S = S; a.H = H; a.cls = cls; a.alpha = alpha; a.scale_log2 = LOG2E / sqrtf((float)dh);
+  switch (dh) {
+    case 16: return launch_rollout<16>(a, B, st);
+    case 32: return launch_rollout<32>(a, B, st);
+    default: return launch_rollout<64>(a, B, st);
+  }
+}

@@ -22,6 +22,7 @@
 #include <string>
 #include <vector>
 
+#include "attn_maps.h"
 #include "common.h"
 #include "iqvit.h"
 #include "prof.h"
@@ -148,6 +149,8 @@ struct iq_model {
   uint64_t last_seed = 0;   // seed of the last training forward; backward regenerates the same masks
   bool last_tr = false;     // whether the last forward applied dropout
   bool last_train_fwd = false;   // a forward has run in this workspace (the one-launch feed-forward's gate bits exist)
+  const void* fwd_ws = nullptr;  // workspace and batch of the last forward that completed its launches (attention read-back)
+  int fwd_batch = 0;
 
   iq_dropout_t bwd_site(uint32_t id, const uint32_t* step_dev, bool tr) const {
     iq_dropout_t d;
@@ -483,6 +486,7 @@ extern "C" int iq_model_forward(iq_model_t* m, const float* src, int batch, void
     m->last_seed = seed;
   }
   const float* P = m->params;
+  m->fwd_ws = nullptr;           // recorded again once every launch below has been issued
 
   // ---- embedding: patchify -> GEMM(+bias +PE, dropout) ; cls rows -------------------------------
   if (c.kind == 0) IQ_TRY(iq_patchify(src, ws + w.patches, 0, B, c.in_channels, c.img_h, c.img_w, c.patch, m->Ppad, stream), "patchify");
@@ -566,7 +570,62 @@ extern "C" int iq_model_forward(iq_model_t* m, const float* src, int batch, void
                        c.num_classes, m->pool, stream), "head");
   }
   if (enc_out) bf16_to_f32_kernel<<<blocks_for((size_t)M * D / 8), 256, 0, st>>>((const bf16*)x, enc_out, (size_t)M * D / 8);
-  return iq_launch_status();
+  const int rc = iq_launch_status();
+  if (rc == IQ_OK) { m->fwd_ws = workspace; m->fwd_batch = batch; }
+  return rc;
+}
+
+// The attention read-back needs the q,k,v and lse of a forward of THIS batch in THIS workspace (plan_ws places them by batch).
+static int maps_check(iq_model_t* m, const void* workspace, size_t ws_bytes, int batch, const char* what, WsPlan* w) {
+  if (!workspace || batch <= 0) return fail(m, IQ_ERR_ARG, std::string(what) + ": bad arguments");
+  if (!m->fwd_ws) return fail(m, IQ_ERR_ARG, std::string(what) + ": no forward has run in a workspace");
+  if (m->fwd_ws != workspace) return fail(m, IQ_ERR_ARG, std::string(what) + ": the last forward ran in another workspace");
+  if (m->fwd_batch != batch)
+    return fail(m, IQ_ERR_ARG, std::string(what) + ": the last forward in this workspace had batch " + std::to_string(m->fwd_batch) +
+                                   ", not " + std::to_string(batch));
+  *w = plan_ws(m, batch);
+  if (ws_bytes < w->total) return fail(m, IQ_ERR_ARG, std::string(what) + ": workspace too small");
+  return IQ_OK;
+}
+
+extern "C" int iq_model_attention(iq_model_t* m, const void* workspace, size_t ws_bytes, int batch, int layer, int rows,
+                                  int heads, float* out, long out_bstride, iq_stream_t stream) {
+  if (!m) return IQ_ERR_ARG;
+  WsPlan w;
+  const int rc = maps_check(m, workspace, ws_bytes, batch, "attention", &w);
+  if (rc != IQ_OK) return rc;
+  if (layer < 0 || layer >= m->c.n_layers) return fail(m, IQ_ERR_ARG, "attention: layer index out of range");
+  if (rows < 0 || rows > 2 || heads < 0 || heads > 1) return fail(m, IQ_ERR_ARG, "attention: rows must be 0, 1 or 2 and heads 0 or 1");
+  if (!out) return fail(m, IQ_ERR_ARG, "attention: out is NULL");
+  const int S = m->S, H = m->c.n_head;
+  if (out_bstride < (long)(heads ? 1 : H) * S * (rows == 0 ? S : 1)) return fail(m, IQ_ERR_ARG, "attention: out_bstride too small");
+  const unsigned char* ws = (const unsigned char*)workspace;
+  const WsPlan::L& a = w.layers[layer];
+  IQ_TRY(iq_attn_probs(ws + a.qkv, (const float*)(ws + a.lse), out, out_bstride, batch, S, H, m->dh, rows, heads, stream),
+         "attention probabilities");
+  return IQ_OK;
+}
+
+extern "C" int iq_model_attention_rollout(iq_model_t* m, const void* workspace, size_t ws_bytes, int batch, float alpha,
+                                          float* out, iq_stream_t stream) {
+  if (!m) return IQ_ERR_ARG;
+  WsPlan w;
+  const int rc = maps_check(m, workspace, ws_bytes, batch, "attention rollout", &w);
+  if (rc != IQ_OK) return rc;
+  if (!(alpha >= 0.f && alpha <= 1.f)) return fail(m, IQ_ERR_ARG, "attention rollout: alpha must be in [0, 1]");
+  if (!out) return fail(m, IQ_ERR_ARG, "attention rollout: out is NULL");
+  const unsigned char* ws = (const unsigned char*)workspace;
+  const int L = m->c.n_layers;
+  // the kernel walks the layers with one stride per buffer: plan_ws lays every layer out alike
+  const long qs = L > 1 ? (long)(w.layers[1].qkv - w.layers[0].qkv) : 0, ls = L > 1 ? (long)(w.layers[1].lse - w.layers[0].lse) : 0;
+  for (int l = 0; l < L; ++l)
+    if ((long)(w.layers[l].qkv - w.layers[0].qkv) != l * qs || (long)(w.layers[l].lse - w.layers[0].lse) != l * ls)
+      return fail(m, IQ_ERR_UNSUPPORTED, "attention rollout: workspace layers are not evenly spaced");
+  const size_t q0 = L ? w.layers[0].qkv : 0, l0 = L ? w.layers[0].lse : 0;
+  IQ_TRY(attn_rollout_launch(ws + q0, qs, ws + l0, ls, L, out, batch, m->S, m->c.n_head, m->dh, m->has_cls, alpha,
+                             (hipStream_t)stream),
+         "attention rollout");
+  return IQ_OK;
 }
 
 extern "C" int iq_model_grad_range(const iq_model_t* m, int stage_hi, int stage_lo, size_t* off, size_t* len) {
