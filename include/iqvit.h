@@ -261,6 +261,17 @@ int iq_cls_rows(const float* cls, const float* pe, void* x0, int B, int S, int D
                 iq_stream_t stream);
 int iq_embed_bwd_gather(const void* dx0, void* demb, float* dcls, int B, int S, int tok, int D, int has_cls,
                         const iq_dropout_t* drop, int accumulate, iq_stream_t stream);
+/* Data gradient of the embedding: dsrc = unpatchify(demb . W), the inverse of iq_patchify's layout.  demb bf16 [B*tok, D],
+ * w_bf16 bf16 [D, Kpad] (the padded weight, columns >= P ignored; both 16 B aligned), dsrc fp32 in the input's layout
+ * (kind 0: (B,C,H,W), p x p patches; kind 1: (B,C,L) with L in H, segments of p).  Every element of dsrc is written: input
+ * elements no patch covers (H % p, W % p, L % p) get 0.  Deterministic (no atomics).  IQ_ERR_ARG before any launch for NULL
+ * pointers, a bad kind, D % 8, Kpad % 8 or Kpad < P. */
+int iq_embed_dgrad(const void* demb, const void* w_bf16, int Kpad, float* dsrc, int kind, int B, int C, int H, int W, int p,
+                   int D, iq_stream_t stream);
+/* One L-infinity attack step over n fp32 elements: x_adv <- clamp(clamp(x_adv + alpha*sign(grad), x0-eps, x0+eps), lo, hi),
+ * sign(0) = 0; lo / hi = NaN means no bound.  alpha, eps >= 0 and finite, lo <= hi. */
+int iq_linf_step(float* x_adv, const float* grad, const float* x0, float alpha, float eps, float lo, float hi, size_t n,
+                 iq_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * Classification head + loss.
@@ -349,6 +360,14 @@ int iq_model_backward(iq_model_t* m, const float* dlogits, const float* denc, in
  * iq_model_grad_range below); vit-vs-raw-iq_amd/trainer.py issues one asynchronous all-reduce per range. */
 /* flat-gradient range [*off, *off+*len) written by stages [stage_lo, stage_hi] (DDP buckets) */
 int iq_model_grad_range(const iq_model_t* m, int stage_hi, int stage_lo, size_t* off, size_t* len);
+/* Gradient with respect to the model input of the last forward in `workspace` (same batch; refused otherwise, as
+ * iq_model_attention): the whole chain from dlogits [B,K] and/or denc [B,S,D] down to the embedding, then
+ * iq_embed_dgrad.  dsrc fp32 in the input's layout is WRITTEN.  Without IQ_BWD_PARAM_GRADS no parameter gradient is formed
+ * and the plan may be bound without a gradient buffer; with it the flat gradient is written exactly as
+ * iq_model_backward(accumulate=0, n_layers+1, 0) writes it.  dsrc does not depend on the flag. */
+#define IQ_BWD_PARAM_GRADS 1
+int iq_model_backward_input(iq_model_t* m, const float* dlogits, const float* denc, int batch, void* workspace,
+                            size_t ws_bytes, float* dsrc, int flags, iq_stream_t stream);
 /* Attention read-back after iq_model_forward(..., batch, workspace): layer `layer`'s attention probabilities from that forward
  * (see iq_attn_probs for rows / heads / out) -- the per-layer `score` of ScaleDotProductAttention.forward
  * (V/models/layers/scale_dot_product_attention.py:25-39) that MultiHeadAttention.forward drops

@@ -8,6 +8,8 @@ Import name: `vit_vs_raw_iq_amd` (the directory name contains hyphens; the repo-
   trainer   -- fused native training step (CE + backward + clip + AdamW) and data-parallel driver
   data      -- seeded synthetic IQ frames (the reference ships no data)
   attention_maps -- per-layer attention probabilities and attention rollout from the fused forward pass
+  saliency  -- input gradients of the fused model: gradient saliency, integrated gradients
+  adversarial -- FGSM / PGD attacks on the model input and accuracy-versus-epsilon curves
   _native   -- ctypes binding of include/iqvit.h  (libiqvit.so; no fallback)
   ViT.models.amc_transformer / transformer_rawIQ.models.transformer_rawIQ
             -- import paths used by the reference's scripts (hyperparameter_tuning.py:19,37)
@@ -17,8 +19,10 @@ from .modules import (AMCTransformerViT, AMCTransformerRawIQ, EncoderViT, Encode
                       SequenceEmbedding, NativePlan)
 from ._native import IqError, LIB_PATH
 from .attention_maps import attention_maps, attention_rollout, rollout_to_input
+from .saliency import input_gradient, integrated_gradients
+from .adversarial import fgsm, pgd, robustness_curve
 
 __all__ = ["AMCTransformerViT", "AMCTransformerRawIQ", "EncoderViT", "EncoderRawIQ", "EncoderLayer", "LayerNorm",
            "MultiHeadAttention", "PositionwiseFeedForward", "ScaleDotProductAttention", "PatchEmbedding",
            "SequenceEmbedding", "NativePlan", "IqError", "LIB_PATH", "attention_maps", "attention_rollout",
-           "rollout_to_input"]
+           "rollout_to_input", "input_gradient", "integrated_gradients", "fgsm", "pgd", "robustness_curve"]

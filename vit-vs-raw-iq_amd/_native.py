@@ -11,6 +11,8 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("IQ_LIBIQVIT") or os.path.join(_HERE, "libiqvit.so")      # (override: A/B runs of two builds on one box)
 
+BWD_PARAM_GRADS = 1     # iq_model_backward_input flag (IQ_BWD_PARAM_GRADS)
+
 STATUS = {0: "ok", 1: "invalid argument", 2: "unsupported shape/configuration", 3: "HIP launch error"}
 
 
@@ -87,6 +89,8 @@ SIGNATURES = {
     "iq_patchify": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "iq_cls_rows": (_I, [_P, _P, _P, _I, _I, _I, C.POINTER(Dropout), _P]),
     "iq_embed_bwd_gather": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, C.POINTER(Dropout), _I, _P]),
+    "iq_embed_dgrad": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "iq_linf_step": (_I, [_P, _P, _P, _F, _F, _F, _F, _Z, _P]),
     "iq_head_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "iq_ce_fwd_bwd": (_I, [_P, _P, _I, _I, _F, _F, _P, _P, _P, _P]),
     "iq_head_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
@@ -112,6 +116,7 @@ SIGNATURES = {
     "iq_model_forward": (_I, [_P, _P, _I, _P, _Z, _I, _U64, _U32, _P, _P, _P]),
     "iq_model_backward": (_I, [_P, _P, _P, _I, _P, _Z, _I, _I, _I, _P]),
     "iq_model_grad_range": (_I, [_P, _I, _I, C.POINTER(_Z), C.POINTER(_Z)]),
+    "iq_model_backward_input": (_I, [_P, _P, _P, _I, _P, _Z, _P, _I, _P]),
     "iq_model_attention": (_I, [_P, _P, _Z, _I, _I, _I, _I, _P, C.c_long, _P]),
     "iq_model_attention_rollout": (_I, [_P, _P, _Z, _I, _F, _P, _P]),
     "iq_prof_enable": (_I, [_I]),

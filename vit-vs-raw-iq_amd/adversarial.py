@@ -1,0 +1,145 @@
+"""L-infinity attacks on the model input (FGSM, PGD) and accuracy-versus-epsilon curves.
+
+Every step runs on native kernels only, with no host synchronisation inside a chunk's loop: an eval forward of the plan
+model.forward uses, iq_ce_fwd_bwd (smoothing 0) for d CE / d logits, iq_model_backward_input without parameter gradients,
+then iq_linf_step:  x <- clamp(clamp(x + alpha sign(g), x0 - eps, x0 + eps), lo, hi).  Chunks of `batch` frames are attacked
+one after another in the plan's workspace.  The module's `training` flag and every `p.grad` are left alone; a pending
+backward() of an earlier forward raises afterwards, as after any later forward.  There is no CPU path.
+
+  fgsm(model, src, labels, eps, clip=None, batch=256)         one step of size eps (Goodfellow et al. 2015)
+  pgd(model, src, labels, eps, alpha, steps, random_start=False, seed=0, clip=None, batch=256)
+                                                              `steps` steps of size alpha projected on the eps ball (Madry et
+                                                              al. 2018); random_start draws the start uniformly in the ball
+  robustness_curve(model, x, y, eps_list, attack="fgsm"|"pgd", batch=256, **kw)
+                                                              top-1 accuracy (float) per eps; eps 0 = the clean accuracy.
+                                                              PGD defaults: steps 10, alpha 2.5 eps / steps.
+
+eps and alpha are in the units of the model's input, the z-scored frame (data.py): one unit is one standard deviation of the
+channel.  clip = (lo, hi) bounds every element after each step (None or a None bound: unbounded).
+"""
+from __future__ import annotations
+
+import math
+import numbers
+import operator
+
+import torch
+
+from . import _native as N
+from .saliency import _batch, _ce_grad, _classes, _forward, _input_grad, _resolve
+
+
+def _nonneg(v, what):
+    if not isinstance(v, numbers.Real) or isinstance(v, bool) or not math.isfinite(float(v)) or float(v) < 0:
+        raise ValueError(f"{what} must be a finite number >= 0, got {v!r}")
+    return float(v)
+
+
+def _clip(clip):
+    if clip is None:
+        return math.nan, math.nan
+    try:
+        lo, hi = clip
+    except (TypeError, ValueError):
+        raise ValueError(f"clip must be None or (lo, hi), got {clip!r}") from None
+    lo = math.nan if lo is None else float(lo)
+    hi = math.nan if hi is None else float(hi)
+    if lo == lo and hi == hi and lo > hi:
+        raise ValueError(f"clip lower bound {lo} is above the upper bound {hi}")
+    return lo, hi
+
+
+def _step(x, g, x0, alpha, eps, lo, hi):
+    N.check(N.lib().iq_linf_step(N.ptr(x), N.ptr(g), N.ptr(x0), alpha, eps, lo, hi, x.numel(), N.stream_handle()), "iq_linf_step")
+
+
+def _prepare(model, src, labels, batch):
+    enc, plan_of, K = _resolve(model)
+    batch = _batch(batch)
+    n = src.shape[0] if isinstance(src, torch.Tensor) and src.dim() > 0 else 0
+    lab = _classes(labels, n, K, "labels")
+    return enc, plan_of, lab, batch
+
+
+def _attack(plan, src, lab, eps, alpha, steps, start, lo, hi, batch):
+    out = start
+    with torch.no_grad():
+        for i in range(0, src.shape[0], batch):
+            x0, xa, y = src[i:i + batch], out[i:i + batch], lab[i:i + batch].contiguous()
+            for _ in range(steps):
+                logits = _forward(plan, xa)
+                _step(xa, _input_grad(plan, xa, _ce_grad(plan, logits, y)), x0, alpha, eps, lo, hi)
+    return out
+
+
+def fgsm(model, src, labels, eps, clip=None, batch=256):
+    enc, plan_of, lab, batch = _prepare(model, src, labels, batch)
+    eps = _nonneg(eps, "eps")
+    lo, hi = _clip(clip)
+    src = enc._expect(src)
+    plan = plan_of()
+    return _attack(plan, src, lab.to(src.device), eps, eps, 1, src.clone(), lo, hi, batch)
+
+
+def pgd(model, src, labels, eps, alpha, steps, random_start=False, seed=0, clip=None, batch=256):
+    enc, plan_of, lab, batch = _prepare(model, src, labels, batch)
+    eps = _nonneg(eps, "eps")
+    alpha = _nonneg(alpha, "alpha")
+    steps = operator.index(steps)
+    if steps < 1:
+        raise ValueError(f"steps must be >= 1, got {steps}")
+    seed = operator.index(seed)
+    lo, hi = _clip(clip)
+    src = enc._expect(src)
+    plan = plan_of()
+    start = src.clone()
+    if random_start and eps > 0:
+        g = torch.Generator(device=src.device)
+        g.manual_seed(seed)
+        noise = torch.rand(src.shape, generator=g, device=src.device, dtype=torch.float32).mul_(2 * eps).sub_(eps)
+        start = torch.minimum(torch.maximum(src + noise, src - eps), src + eps)
+        if lo == lo:
+            start.clamp_(min=lo)
+        if hi == hi:
+            start.clamp_(max=hi)
+    return _attack(plan, src, lab.to(src.device), eps, alpha, steps, start, lo, hi, batch)
+
+
+def robustness_curve(model, x, y, eps_list, attack="fgsm", batch=256, **kw):
+    if attack not in ("fgsm", "pgd"):
+        raise ValueError(f"attack must be 'fgsm' or 'pgd', got {attack!r}")
+    eps_list = [_nonneg(e, "eps") for e in eps_list]
+    allowed = {"clip"} if attack == "fgsm" else {"clip", "alpha", "steps", "random_start", "seed"}
+    extra = set(kw) - allowed
+    if extra:
+        raise TypeError(f"unexpected keyword arguments for attack={attack!r}: {sorted(extra)}")
+    steps = operator.index(kw.get("steps", 10))
+    if steps < 1:
+        raise ValueError(f"steps must be >= 1, got {steps}")
+    if kw.get("alpha") is not None:
+        _nonneg(kw["alpha"], "alpha")
+    _clip(kw.get("clip"))
+    enc, plan_of, lab, batch = _prepare(model, x, y, batch)
+    x = enc._expect(x)
+    plan = plan_of()
+    lab = lab.to(x.device)
+
+    def accuracy(xs):
+        correct = torch.zeros((), dtype=torch.int64, device=x.device)
+        with torch.no_grad():
+            for i in range(0, xs.shape[0], batch):
+                correct += (_forward(plan, xs[i:i + batch]).argmax(1) == lab[i:i + batch]).sum()
+        return correct.item() / max(1, xs.shape[0])
+
+    out = []
+    for eps in eps_list:
+        if eps == 0:
+            out.append(accuracy(x))
+        elif attack == "fgsm":
+            out.append(accuracy(fgsm(model, x, lab, eps, clip=kw.get("clip"), batch=batch)))
+        else:
+            alpha = kw.get("alpha")
+            alpha = 2.5 * eps / steps if alpha is None else alpha
+            out.append(accuracy(pgd(model, x, lab, eps, alpha, steps, random_start=kw.get("random_start", False),
+                                    seed=kw.get("seed", 0), clip=kw.get("clip"), batch=batch)))
+    return out

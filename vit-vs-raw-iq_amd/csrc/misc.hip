@@ -747,3 +747,60 @@ extern "C" int iq_frames_preprocess(const float* raw, float* out, int n_frames, 
   frames_preprocess_kernel<<<(int)nb, 256, 0, st>>>(raw, out, n, len, take, stats[0], stats[1], stats[2], stats[3]);
   return iq_launch_status();
 }
+
+// ---------------------------------------------------------------------------------------------
+// data-gradient-only pieces of the model backward (iq_model_backward_input without IQ_BWD_PARAM_GRADS): the head's d(x_L)
+// and the embedding gather without the CLS gradient -- the same kernels, launched alone
+// ---------------------------------------------------------------------------------------------
+int head_bwd_dx_launch(const float* dlogits, const float* featn, const float* hstat, const float* ln_g, const float* W, void* dx,
+                       int B, int S, int D, int K, int pool, hipStream_t st) {
+  IQ_PROF(IQ_FAM_MISC, st);
+  if (B <= 0) return IQ_OK;
+  head_bwd_dx_kernel<<<B, 256, D * sizeof(float), st>>>(dlogits, featn, hstat, ln_g, W, (bf16*)dx, S, D, K, pool);
+  return iq_launch_status();
+}
+
+int embed_bwd_gather_launch(const void* dx0, void* demb, int B, int S, int tok, int D, int has_cls, const iq_dropout_t* drop,
+                            hipStream_t st) {
+  IQ_PROF(IQ_FAM_MISC, st);
+  if (B <= 0) return IQ_OK;
+  int on; IqRng r; uint32_t th; float sc;
+  fill_rng(drop, &on, &r, &th, &sc);
+  const size_t n = (size_t)B * tok * (D / 8);
+  embed_bwd_gather_kernel<<<grid_for(n, 256, 4096), 256, 0, st>>>((const bf16*)dx0, (bf16*)demb, B, S, tok, D, has_cls ? 1 : 0,
+                                                                  on, r, th, sc);
+  return iq_launch_status();
+}
+
+// ---------------------------------------------------------------------------------------------
+// L-infinity attack step: x <- clamp(clamp(x + alpha sign(g), x0 - eps, x0 + eps), lo, hi); NaN bound = none.
+// Written as torch writes it (sign(0) = 0; fmin/fmax order of the two clamps), so the result is bit-exact against
+// x.add(alpha * g.sign()).clamp(x0 - eps, x0 + eps).clamp(lo, hi) in fp32.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void linf_step_kernel(float* __restrict__ x, const float* __restrict__ g, const float* __restrict__ x0,
+                                                        float alpha, float eps, float lo, float hi, int has_lo, int has_hi, long n) {
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const float gv = g[i];
+    const float s = gv > 0.f ? 1.f : gv < 0.f ? -1.f : 0.f;
+    float v = __fadd_rn(x[i], __fmul_rn(alpha, s));
+    const float c = x0[i];
+    v = fminf(fmaxf(v, __fsub_rn(c, eps)), __fadd_rn(c, eps));
+    if (has_lo) v = fmaxf(v, lo);
+    if (has_hi) v = fminf(v, hi);
+    x[i] = v;
+  }
+}
+
+extern "C" int iq_linf_step(float* x_adv, const float* grad, const float* x0, float alpha, float eps, float lo, float hi, size_t n,
+                            iq_stream_t stream) {
+  if (!x_adv || !grad || !x0) return IQ_ERR_ARG;
+  if (!(alpha >= 0.f) || !(eps >= 0.f) || !(alpha < INFINITY) || !(eps < INFINITY)) return IQ_ERR_ARG;
+  const bool has_lo = lo == lo, has_hi = hi == hi;
+  if (has_lo && has_hi && lo > hi) return IQ_ERR_ARG;
+  if (n == 0) return IQ_OK;
+  hipStream_t st = (hipStream_t)stream;
+  IQ_PROF(IQ_FAM_MISC, st);
+  linf_step_kernel<<<grid_for(n, 256, 8192), 256, 0, st>>>(x_adv, grad, x0, alpha, eps, lo, hi, has_lo ? 1 : 0, has_hi ? 1 : 0,
+                                                           (long)n);
+  return iq_launch_status();
+}

@@ -27,6 +27,12 @@
 #include "iqvit.h"
 #include "prof.h"
 
+// data-gradient-only launches of misc.hip (the head's d(x_L); the embedding gather without the CLS gradient)
+int head_bwd_dx_launch(const float* dlogits, const float* featn, const float* hstat, const float* ln_g, const float* W, void* dx,
+                       int B, int S, int D, int K, int pool, hipStream_t st);
+int embed_bwd_gather_launch(const void* dx0, void* demb, int B, int S, int tok, int D, int has_cls, const iq_dropout_t* drop,
+                            hipStream_t st);
+
 namespace {
 
 struct Entry {
@@ -639,10 +645,13 @@ extern "C" int iq_model_grad_range(const iq_model_t* m, int stage_hi, int stage_
   return IQ_OK;
 }
 
-extern "C" int iq_model_backward(iq_model_t* m, const float* dlogits, const float* denc, int batch, void* workspace,
-                                 size_t ws_bytes, int accumulate, int stage_hi, int stage_lo, iq_stream_t stream) {
-  if (!m) return IQ_ERR_ARG;
-  if (!m->params || !m->grads || !m->shadow) return fail(m, IQ_ERR_ARG, "backward: model not bound (grads required)");
+// The backward chain.  pgrads = false (iq_model_backward_input without IQ_BWD_PARAM_GRADS): the same data-gradient launches in
+// the same order, none of the parameter-gradient ones (head dW / db / LN, the layers' grouped weight gradients + their slab and
+// LayerNorm reduce, the CLS gradient, the embedding weight gradient); nothing is read from or written to m->grads.  The data
+// chain never reads what a weight-gradient launch writes, so its bits do not depend on pgrads.
+static int backward_impl(iq_model_t* m, const float* dlogits, const float* denc, int batch, void* workspace, size_t ws_bytes,
+                         int accumulate, int stage_hi, int stage_lo, bool pgrads, iq_stream_t stream) {
+  if (!m->params || (pgrads && !m->grads) || !m->shadow) return fail(m, IQ_ERR_ARG, "backward: model not bound (grads required)");
   if (!workspace || batch <= 0) return fail(m, IQ_ERR_ARG, "backward: bad arguments");
   const iq_model_cfg_t& c = m->c;
   const int Lr = c.n_layers;
@@ -662,12 +671,15 @@ extern "C" int iq_model_backward(iq_model_t* m, const float* dlogits, const floa
 
   if (stage_hi == Lr + 1) {
     if (!dlogits && !denc) return fail(m, IQ_ERR_ARG, "backward: dlogits or denc required at the head stage");
-    if (dlogits) {
+    if (dlogits && !pgrads) {
+      IQ_TRY(head_bwd_dx_launch(dlogits, (const float*)(ws + w.head_feat), (const float*)(ws + w.head_stat),
+                                m->head_ln ? P + m->hln_g : nullptr, P + m->head_w, ws + w.gA, B, S, D, K, m->pool, st), "head bwd (dx)");
+    } else if (dlogits) {
       IQ_TRY(iq_head_bwd(dlogits, (const float*)(ws + w.head_feat), (const float*)(ws + w.head_stat),
                          m->head_ln ? P + m->hln_g : nullptr, m->head_ln ? P + m->hln_b : nullptr, P + m->head_w,
                          G + m->head_w, G + m->head_b, m->head_ln ? G + m->hln_g : nullptr,
                          m->head_ln ? G + m->hln_b : nullptr, ws + w.gA, B, S, D, K, m->pool, accumulate, stream), "head bwd");
-    } else if (!accumulate) {
+    } else if (!accumulate && pgrads) {
       (void)hipMemsetAsync(G + m->head_begin, 0, (m->nparam - m->head_begin) * sizeof(float), st);
     }
     if (denc) f32_into_bf16_kernel<<<blocks_for((size_t)M * D / 8), 256, 0, st>>>(denc, (bf16*)(ws + w.gA), (size_t)M * D / 8, dlogits ? 1 : 0);
@@ -748,7 +760,7 @@ extern "C" int iq_model_backward(iq_model_t* m, const float* dlogits, const floa
     IQ_TRY(iq_attn_bwd(ws + a.qkv, ws + a.att, ws + w.gAtt, (const float*)(ws + a.lse), gQKV, B, S, H, m->dh, stream), "attention bwd");
     // The four weight gradients of the layer, BEFORE the QKV data gradient: fused with the norm2 backward of the layer
     // below, that GEMM overwrites gZ / gY and the norm2 partial rows, which the weight gradients / their reduce still read.
-    IQ_TRY(iq_gemm_bf16_wgrad_grouped(wg, 4, M, wws, w.wgrad_ws_bytes, accumulate, 0, lnseg, 4, stream), "layer weight gradients");
+    if (pgrads) IQ_TRY(iq_gemm_bf16_wgrad_grouped(wg, 4, M, wws, w.wgrad_ws_bytes, accumulate, 0, lnseg, 4, stream), "layer weight gradients");
     // ... unless the layer below takes it into its own chain launch (iq_qkv_dgrad_ffn_chain_bwd)
     deferred = l > 0 && fuse2 && chain && post && use_chain_pre(M) >= 3 && sidx - 1 >= stage_lo;
     if (deferred) continue;
@@ -767,6 +779,10 @@ extern "C" int iq_model_backward(iq_model_t* m, const float* dlogits, const floa
   }
   if (stage_lo == 0) {
     const iq_dropout_t dr0 = m->bwd_site(0, step_dev, tr);
+    if (!pgrads) {
+      IQ_TRY(embed_bwd_gather_launch(ws + w.gA, ws + w.demb, B, S, m->tok, D, m->has_cls, &dr0, st), "embedding bwd gather");
+      return iq_launch_status();
+    }
     IQ_TRY(iq_embed_bwd_gather(ws + w.gA, ws + w.demb, m->has_cls ? G + m->cls : nullptr, B, S, m->tok, D, m->has_cls,
                                &dr0, accumulate, stream), "embedding bwd gather");
     if (m->Ppad == m->P) {
@@ -781,4 +797,32 @@ extern "C" int iq_model_backward(iq_model_t* m, const float* dlogits, const floa
     }
   }
   return iq_launch_status();
+}
+
+extern "C" int iq_model_backward(iq_model_t* m, const float* dlogits, const float* denc, int batch, void* workspace,
+                                 size_t ws_bytes, int accumulate, int stage_hi, int stage_lo, iq_stream_t stream) {
+  if (!m) return IQ_ERR_ARG;
+  return backward_impl(m, dlogits, denc, batch, workspace, ws_bytes, accumulate, stage_hi, stage_lo, true, stream);
+}
+
+extern "C" int iq_model_backward_input(iq_model_t* m, const float* dlogits, const float* denc, int batch, void* workspace,
+                                       size_t ws_bytes, float* dsrc, int flags, iq_stream_t stream) {
+  if (!m) return IQ_ERR_ARG;
+  if (flags & ~IQ_BWD_PARAM_GRADS) return fail(m, IQ_ERR_ARG, "backward_input: unknown flags");
+  if (!dsrc) return fail(m, IQ_ERR_ARG, "backward_input: dsrc is NULL");
+  if (!dlogits && !denc) return fail(m, IQ_ERR_ARG, "backward_input: dlogits or denc required");
+  const bool pgrads = (flags & IQ_BWD_PARAM_GRADS) != 0;
+  if (!m->params || !m->shadow || !m->pe) return fail(m, IQ_ERR_ARG, "backward_input: model not bound");
+  if (pgrads && !m->grads) return fail(m, IQ_ERR_ARG, "backward_input: IQ_BWD_PARAM_GRADS needs a bound gradient buffer");
+  WsPlan w;
+  const int rc = maps_check(m, workspace, ws_bytes, batch, "backward_input", &w);
+  if (rc != IQ_OK) return rc;
+  const int rb = backward_impl(m, dlogits, denc, batch, workspace, ws_bytes, 0, m->c.n_layers + 1, 0, pgrads, stream);
+  if (rb != IQ_OK) return rb;
+  const iq_model_cfg_t& c = m->c;
+  unsigned char* ws = (unsigned char*)workspace;
+  const int kind = c.kind, H = kind == 0 ? c.img_h : c.seq_length, W = kind == 0 ? c.img_w : 0, p = kind == 0 ? c.patch : c.conv_k;
+  IQ_TRY(iq_embed_dgrad(ws + w.demb, m->shadow + m->sh_embw, m->Ppad, dsrc, kind, batch, c.in_channels, H, W, p, c.d_model, stream),
+         "embedding data gradient");
+  return IQ_OK;
 }

@@ -11,7 +11,7 @@ the per-op C ABI of include/iqvit.h and with an autograd backward through the ma
   attention      ScaleDotProductAttention.forward      V/models/layers/scale_dot_product_attention.py:18-39
                  (+ split / concat, multi_head_attention.py:34-47)            iq_attn_fwd / iq_attn_bwd
   patch_embed    PatchEmbedding / SequenceEmbedding    V/.../patch_embedding.py:11-15, R/.../patch_embedding.py:47-60
-                                                                              iq_patchify + iq_gemm_bf16_nt
+                                                                              iq_patchify + iq_gemm_bf16_nt / iq_embed_dgrad
 
 Mixed precision is the build's stated policy: fp32 tensors in and out (like the reference), bf16 operands and fp32
 accumulation inside.  GPU tensors only -- there is no CPU path.
@@ -22,6 +22,7 @@ import ctypes as C
 import math
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _native as N
 
@@ -218,9 +219,36 @@ def attention_probabilities(q, k, mask=None):
 
 
 # ------------------------------------------------------------------------------------------------
+class _EmbedInputGradFn(torch.autograd.Function):
+    """Identity on the embedding output `out` that adds the input's gradient: d(x) = unpatchify(d(out) . W) through
+    iq_embed_dgrad (bf16 operands, fp32 accumulation; input elements no patch covers get 0).  The weight and bias gradients
+    keep flowing through `out` (the `linear` that produced it)."""
+
+    @staticmethod
+    def forward(ctx, out, x, w2, kind, patch, dims):
+        ctx.save_for_backward(w2)
+        ctx.kind, ctx.patch, ctx.dims, ctx.x_shape = kind, patch, dims, x.shape
+        return out.view_as(out)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout):
+        if gout is None or not ctx.needs_input_grad[1]:
+            return gout, None, None, None, None, None
+        (w2,) = ctx.saved_tensors
+        L = N.lib()
+        D, Kpad = w2.shape
+        g = _bf(gout).view(-1, D)
+        dx = torch.empty(ctx.x_shape, dtype=torch.float32, device=gout.device)
+        N.check(L.iq_embed_dgrad(g.data_ptr(), _bf(w2).data_ptr(), Kpad, dx.data_ptr(), ctx.kind, ctx.x_shape[0], ctx.dims[0],
+                                 ctx.dims[1], ctx.dims[2], ctx.patch, D, N.stream_handle()), "iq_embed_dgrad")
+        return gout, dx, None, None, None, None
+
+
 def patch_embed(x, weight, bias, kind, patch):
     """Non-overlapping conv embedding as patchify + GEMM.  kind 0: x (B,C,H,W), weight (D,C,p,p) -> (B, N, D);
-    kind 1: x (B,C,L), weight (D,C,k) -> (B, L/k, D).  Differentiable w.r.t. weight and bias through `linear`."""
+    kind 1: x (B,C,L), weight (D,C,k) -> (B, L/k, D).  Differentiable w.r.t. weight and bias through `linear`, and w.r.t. x
+    through iq_embed_dgrad."""
     _need_cuda(x, weight, bias)
     L = N.lib()
     D = weight.shape[0]
@@ -242,4 +270,7 @@ def patch_embed(x, weight, bias, kind, patch):
     w2 = weight.reshape(D, P)
     if Kpad != P:
         w2 = torch.nn.functional.pad(w2, (0, Kpad - P))
-    return linear(patches.float(), w2, bias).view(Bn, tok, D)
+    out = linear(patches.float(), w2, bias).view(Bn, tok, D)
+    if torch.is_grad_enabled() and x.requires_grad:
+        out = _EmbedInputGradFn.apply(out, x, w2.detach(), kind, patch, dims)
+    return out

@@ -32,6 +32,7 @@ from typing import Dict, Optional
 
 import torch
 from torch import nn
+from torch.autograd.function import once_differentiable
 
 from . import _native as N
 from . import functional as NF
@@ -381,6 +382,15 @@ class NativePlan:
                                          1 if accumulate else 0, hi, stage_lo, N.stream_handle()),
                 "iq_model_backward", self.h)
 
+    def backward_input(self, batch: int, dlogits, denc, dsrc: torch.Tensor, gflat=None):
+        """d(loss)/d(src) of the last forward into `dsrc` (written); the flat parameter gradient too when `gflat` is given
+        (written as backward(accumulate=False) writes it), else no parameter gradient is formed."""
+        if gflat is not None and gflat is not self.gflat:
+            self._bind_native(gflat)
+        N.check(self.L.iq_model_backward_input(self.h, N.ptr(dlogits), N.ptr(denc), batch, N.ptr(self.ws), self.ws.numel(),
+                                               N.ptr(dsrc), N.BWD_PARAM_GRADS if gflat is not None else 0,
+                                               N.stream_handle()), "iq_model_backward_input", self.h)
+
     def grad_range(self, stage_hi: int, stage_lo: int):
         off, ln = C.c_size_t(), C.c_size_t()
         N.check(self.L.iq_model_grad_range(self.h, stage_hi, stage_lo, C.byref(off), C.byref(ln)), "grad_range")
@@ -411,28 +421,49 @@ class _PlanFn(torch.autograd.Function):
         ctx.batch = src.shape[0]
         ctx.generation = plan.generation
         ctx.nparams = len(params)
+        ctx.src_shape = src.shape
         ctx.set_materialize_grads(False)
         return logits if want == "logits" else enc
 
     @staticmethod
     def backward(ctx, gout):
-        plan: NativePlan = ctx.plan
-        none = (None,) * 5
-        if gout is None:
-            return none + (None,) * ctx.nparams
-        if ctx.generation != plan.generation:
-            raise RuntimeError(
-                "backward() after a later forward() on the same model: the native workspace holding the saved "
-                "activations has been overwritten. Call backward before running the model again.")
-        gout = gout.contiguous().float()
+        if torch.is_grad_enabled():
+            raise RuntimeError("the fused model's backward is not differentiable: backward(create_graph=True) / "
+                               "torch.autograd.grad(..., create_graph=True) through it is not supported (no double backward)")
+        return _plan_backward(ctx, gout)
+
+
+@once_differentiable
+def _plan_backward(ctx, gout):
+    """_PlanFn.backward below its create_graph check."""
+    plan: NativePlan = ctx.plan
+    none = (None,) * 5
+    if gout is None:
+        return none + (None,) * ctx.nparams
+    if ctx.generation != plan.generation:
+        raise RuntimeError(
+            "backward() after a later forward() on the same model: the native workspace holding the saved "
+            "activations has been overwritten. Call backward before running the model again.")
+    gout = gout.contiguous().float()
+    dl, de = (gout, None) if ctx.want == "logits" else (None, gout)
+    if ctx.needs_input_grad[1]:
+        # the input gradient: one native call that forms the parameter gradients too only when some parameter needs them
+        dsrc = torch.empty(ctx.src_shape, dtype=torch.float32, device=gout.device)
+        if not any(ctx.needs_input_grad[5:]):
+            plan.backward_input(ctx.batch, dl, de, dsrc)
+            return (None, dsrc) + (None,) * (3 + ctx.nparams)
         gflat = torch.empty_like(plan.flat)
-        if ctx.want == "logits":
-            plan.backward(ctx.batch, gout, None, gflat)
-        else:
-            plan.backward(ctx.batch, None, gout, gflat)
+        plan.backward_input(ctx.batch, dl, de, dsrc, gflat)
         named = plan._named()
-        grads = plan.grad_views(gflat, [(n, named[n]) for n in ctx.names])
-        return none + tuple(grads)
+        return (None, dsrc, None, None, None) + tuple(plan.grad_views(gflat, [(n, named[n]) for n in ctx.names]))
+    gflat = torch.empty_like(plan.flat)
+    if ctx.want == "logits":
+        plan.backward(ctx.batch, gout, None, gflat)
+    else:
+        plan.backward(ctx.batch, None, gout, gflat)
+    named = plan._named()
+    grads = plan.grad_views(gflat, [(n, named[n]) for n in ctx.names])
+    return none + tuple(grads)
 
 
 def _check_src(src, ndim, what):
@@ -481,7 +512,7 @@ def _run(plan: NativePlan, owner: nn.Module, src, want, training=None):
     for n, p in owner.named_parameters():
         names.append(n)
         params.append(p)
-    needs_grad = torch.is_grad_enabled() and any(p.requires_grad for p in params)
+    needs_grad = torch.is_grad_enabled() and (src.requires_grad or any(p.requires_grad for p in params))
     if needs_grad:
         plan.ensure(src.device)      # re-home BEFORE autograd records the parameter tensors
         return _PlanFn.apply(plan, src, training, want, tuple(names), *params)
