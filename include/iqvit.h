@@ -239,6 +239,19 @@ int iq_attn_bwd_masked(const void* qkv, const void* out, const void* dout, const
  * Same (S, dh) set as iq_attn_supported.  Two calls give the same bits. */
 int iq_attn_probs(const void* qkv, const float* lse, float* out, long out_bstride, int B, int S, int H, int dh,
                   int rows, int heads, iq_stream_t stream);
+/* Gradient-weighted attention (Chefer, Gur & Wolf, "Transformer Interpretability Beyond Attention Visualization", ICCV 2021,
+ * arXiv 2103.15679, eqs. 5-6), for the same matrix: the reference's `score` (V/models/layers/scale_dot_product_attention.py:
+ * 25-39) times the gradient of a scalar y with respect to it.  dout bf16 [B*S, H*dh] is dy/d(concatenated attention-core
+ * output) (head h at columns h*dh, the layout of iq_attn_fwd's out), so dy/dP[q, key] = dout_h[q] . v_h[key].
+ * iq_attn_grad_probs writes G = P * dP (positive 1: max(G, 0) per head, before the head mean; 0: signed) with the rows /
+ * heads / out layout of iq_attn_probs.  iq_attn_relevance_step writes, fp32 [B, S],
+ *   r_out[b,k] = r_in[b,k] + (1/H) sum_h sum_q r_in[b,q] max(P_h[q,k] dP_h[q,k], 0)
+ * i.e. one row step r <- r (I + mean_h max(G_h, 0)) of the relevance rollout; r_in and r_out must not overlap.
+ * Same (S, dh) set as iq_attn_supported; no atomics, two calls give the same bits. */
+int iq_attn_grad_probs(const void* qkv, const float* lse, const void* dout, float* out, long out_bstride, int B, int S,
+                       int H, int dh, int rows, int heads, int positive, iq_stream_t stream);
+int iq_attn_relevance_step(const void* qkv, const float* lse, const void* dout, const float* r_in, float* r_out, int B,
+                           int S, int H, int dh, iq_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * Embedding front end.  iq_patchify turns the fp32 input frame batch into the bf16 GEMM
@@ -383,6 +396,17 @@ int iq_model_attention(iq_model_t* m, const void* workspace, size_t ws_bytes, in
  * out fp32 [B, S]; each row sums to 1.  0 <= alpha <= 1; same refusals as iq_model_attention. */
 int iq_model_attention_rollout(iq_model_t* m, const void* workspace, size_t ws_bytes, int batch, float alpha,
                                float* out, iq_stream_t stream);
+/* Class-specific relevance (Chefer, Gur & Wolf 2021, eqs. 5-6) of that forward, which must have formed logits: the data-only
+ * backward chain of iq_model_backward_input from dlogits [B,K] (one-hot of the class asked about: the gradient of that logit),
+ * no parameter gradient, stopping at layer 0's attention.  As each layer's attention-output gradient appears (top down):
+ *   maps[l] != NULL: iq_attn_grad_probs of layer l into maps[l] (rows / heads / positive / out_bstride as there)
+ *   rel != NULL:     r <- r (I + mean_h max(P_l * dP_l, 0)) with r starting as iq_model_attention_rollout's does;
+ *                    rel fp32 [B, S] receives the final r (= row 0 of R = prod_l (I + A_l), resp. the mean of R's rows)
+ * maps: host array of n_layers device pointers (NULL entries skip the layer) or NULL.  Same refusals as
+ * iq_model_attention, and when rel and every map are NULL. */
+int iq_model_attention_relevance(iq_model_t* m, const float* dlogits, int batch, void* workspace, size_t ws_bytes,
+                                 float* rel, float* const* maps, int rows, int heads, int positive, long out_bstride,
+                                 iq_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * Measurement aid (bench.py roofline leg): when enabled, every entry point above brackets its

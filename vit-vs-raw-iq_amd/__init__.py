@@ -9,6 +9,7 @@ Import name: `vit_vs_raw_iq_amd` (the directory name contains hyphens; the repo-
   data      -- seeded synthetic IQ frames (the reference ships no data)
   attention_maps -- per-layer attention probabilities and attention rollout from the fused forward pass
   saliency  -- input gradients of the fused model: gradient saliency, integrated gradients
+  relevance -- class-specific attention relevance (gradient-weighted rollout) and gradient-weighted attention maps
   adversarial -- FGSM / PGD attacks on the model input and accuracy-versus-epsilon curves
   _native   -- ctypes binding of include/iqvit.h  (libiqvit.so; no fallback)
   ViT.models.amc_transformer / transformer_rawIQ.models.transformer_rawIQ
@@ -20,9 +21,11 @@ from .modules import (AMCTransformerViT, AMCTransformerRawIQ, EncoderViT, Encode
 from ._native import IqError, LIB_PATH
 from .attention_maps import attention_maps, attention_rollout, rollout_to_input
 from .saliency import input_gradient, integrated_gradients
+from .relevance import attention_relevance, grad_attention_maps
 from .adversarial import fgsm, pgd, robustness_curve
 
 __all__ = ["AMCTransformerViT", "AMCTransformerRawIQ", "EncoderViT", "EncoderRawIQ", "EncoderLayer", "LayerNorm",
            "MultiHeadAttention", "PositionwiseFeedForward", "ScaleDotProductAttention", "PatchEmbedding",
            "SequenceEmbedding", "NativePlan", "IqError", "LIB_PATH", "attention_maps", "attention_rollout",
-           "rollout_to_input", "input_gradient", "integrated_gradients", "fgsm", "pgd", "robustness_curve"]
+           "rollout_to_input", "input_gradient", "integrated_gradients", "attention_relevance", "grad_attention_maps", "fgsm",
+           "pgd", "robustness_curve"]

@@ -85,6 +85,8 @@ SIGNATURES = {
     "iq_attn_fwd_masked": (_I, [_P, _P, _P, _P, C.c_long, _I, _I, _I, _I, _P]),
     "iq_attn_bwd_masked": (_I, [_P, _P, _P, _P, _P, _P, C.c_long, _I, _I, _I, _I, _P]),
     "iq_attn_probs": (_I, [_P, _P, _P, C.c_long, _I, _I, _I, _I, _I, _I, _P]),
+    "iq_attn_grad_probs": (_I, [_P, _P, _P, _P, C.c_long, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "iq_attn_relevance_step": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "iq_frames_preprocess": (_I, [_P, _P, _I, _I, _I, C.POINTER(C.c_float), _P]),
     "iq_patchify": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "iq_cls_rows": (_I, [_P, _P, _P, _I, _I, _I, C.POINTER(Dropout), _P]),
@@ -119,6 +121,7 @@ SIGNATURES = {
     "iq_model_backward_input": (_I, [_P, _P, _P, _I, _P, _Z, _P, _I, _P]),
     "iq_model_attention": (_I, [_P, _P, _Z, _I, _I, _I, _I, _P, C.c_long, _P]),
     "iq_model_attention_rollout": (_I, [_P, _P, _Z, _I, _F, _P, _P]),
+    "iq_model_attention_relevance": (_I, [_P, _P, _I, _P, _Z, _P, C.POINTER(_P), _I, _I, _I, C.c_long, _P]),
     "iq_prof_enable": (_I, [_I]),
     "iq_prof_collect": (_I, [C.POINTER(C.c_double), C.POINTER(C.c_longlong)]),
     "iq_prof_kernels": (_Z, [C.c_char_p, _Z, _I]),

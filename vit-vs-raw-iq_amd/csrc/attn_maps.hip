@@ -18,6 +18,13 @@
 //   rows 1, 2         thread `col` sums its key column of the tile (query 0 only, resp. every real query, in order)
 // No atomics: every output element is written by one thread of one workgroup and every sum runs in a fixed order, so two
 // calls give the same bits.
+//
+// Gradient-weighted maps and the relevance step (Chefer, Gur & Wolf, ICCV 2021, arXiv 2103.15679, eqs. 5-6) take the gradient
+// dO of the concatenated attention-core output as well: dP[q, key] = dO_h[q].v_h[key] is a second mfma_f32_16x16x32_bf16 product
+// of the same tile shape (V chunk as A, dO block as B), and G = P * dP (clamped at 0 per head when asked) replaces P above.
+// The relevance step r_out = r_in + r_in * mean_h max(G_h, 0) runs one workgroup per (frame, block of 128 keys): wave w owns
+// key tile w, its lanes accumulate r_in[q] * max(G, 0) over heads and query tiles in registers and the 16 query lanes of a
+// key are reduced by a fixed butterfly at the end.
 #include <stdint.h>
 
 #include "attn_maps.h"
@@ -145,10 +152,42 @@ struct ProbsArgs {
   int S, H, rows, heads;
   int nhg, nqg;        // head groups / query-block groups per frame in the grid (1: the workgroup loops over all of them)
   float scale_log2;
+  const bf16* dout;    // attn_grad_probs_kernel only: dO [B*S, H*dh] and whether G is clamped at 0
+  int positive;
 };
 
+// The raw products of this wave's tiles in the layout of tile_probs: d[u][j] = A tile (wave + 8 j) x B half u.
 template <int DH>
-__global__ __launch_bounds__(PM_THREADS) void attn_probs_kernel(ProbsArgs a) {
+__device__ __forceinline__ void tile_dots(const bf16* Bs, const bf16* As, bool u1, int kc, int wave, int lane, f32x4 d[2][KTW]) {
+  constexpr int KS = PmCfg<DH>::KS;
+  const int c16 = lane & 15;
+  bf16x8 bf[2][KS];
+#pragma unroll
+  for (int u = 0; u < 2; ++u)
+#pragma unroll
+    for (int s = 0; s < KS; ++s) bf[u][s] = row_frag<DH>(Bs, u * 16 + c16, s, lane);
+#pragma unroll
+  for (int j = 0; j < KTW; ++j) {
+    const int kt = wave + PM_WAVES * j;
+    d[0][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    d[1][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (kt * 16 >= kc) continue;
+    bf16x8 af[KS];
+#pragma unroll
+    for (int s = 0; s < KS; ++s) af[s] = row_frag<DH>(As, kt * 16 + c16, s, lane);
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      if (u == 1 && !u1) continue;
+#pragma unroll
+      for (int s = 0; s < KS; ++s) d[u][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[s], bf[u][s], d[u][j], 0, 0, 0);
+    }
+  }
+}
+
+// GRAD = false: P (attn_probs_kernel).  GRAD = true: G = P * dP, max(G, 0) when a.positive (attn_grad_probs_kernel): after P,
+// the dO block and the V chunk are staged where Q and K were and dP is formed in the same layout.
+template <int DH, bool GRAD>
+__device__ __forceinline__ void probs_body(const ProbsArgs& a) {
   using Cf = PmCfg<DH>;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   bf16* Qs = reinterpret_cast<bf16*>(smem);
@@ -189,6 +228,23 @@ __global__ __launch_bounds__(PM_THREADS) void attn_probs_kernel(ProbsArgs a) {
       f32x4 p[2][KTW];
       tile_probs<DH>(Qs, Ks, lq, a.rows != 1 && q0 + 16 < S, kc, k0, S, a.scale_log2, wave, lane, p);
       __syncthreads();                           // Qs / Ks free for the next item
+      if (GRAD) {
+        stage<DH>(Qs, a.dout + (long)b * S * D + h * DH, D, q0, QB, S, tid);
+        stage<DH>(Ks, hq + 2 * D, ldg, k0, (kc + 15) / 16 * 16, S, tid);
+        __syncthreads();
+        f32x4 dp[2][KTW];
+        tile_dots<DH>(Qs, Ks, a.rows != 1 && q0 + 16 < S, kc, wave, lane, dp);
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < KTW; ++j)
+#pragma unroll
+          for (int u = 0; u < 2; ++u)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const float g = p[u][j][r] * dp[u][j][r];    // keys >= S: p is 0; queries >= S are never read
+              p[u][j][r] = a.positive ? fmaxf(g, 0.f) : g;
+            }
+      }
       const int nrow = a.rows == 1 ? 1 : min(QB, S - q0);
       if (a.rows == 0 && a.heads == 1) {
         const float inv = 1.0f / H;
@@ -223,6 +279,12 @@ __global__ __launch_bounds__(PM_THREADS) void attn_probs_kernel(ProbsArgs a) {
     }
   }
 }
+
+template <int DH>
+__global__ __launch_bounds__(PM_THREADS) void attn_probs_kernel(ProbsArgs a) { probs_body<DH, false>(a); }
+
+template <int DH>
+__global__ __launch_bounds__(PM_THREADS) void attn_grad_probs_kernel(ProbsArgs a) { probs_body<DH, true>(a); }
 
 // Rollout: one workgroup per frame, r and the next r in LDS.  Per layer (top down), chunk of keys, head and query block, the
 // P tile goes to LDS and thread `col` adds sum_q r[q] P[q, col] in order; the chunk's new r is
@@ -293,9 +355,109 @@ __global__ __launch_bounds__(PM_THREADS) void attn_rollout_kernel(RolloutArgs a)
   for (int i = tid; i < S; i += PM_THREADS) a.out[(long)b * S + i] = r[i];
 }
 
-template <int DH> size_t probs_lds() { return (size_t)QB * PmCfg<DH>::LD * 2 + (size_t)KC * PmCfg<DH>::LD * 2 + (size_t)QB * PLD * 4; }
+// Relevance step: one workgroup per (frame, block of RKB keys).  Per head the K and V rows of the block are staged once; per
+// chunk of RQC queries the Q and dO rows.  Wave w holds key tile w (its K and V fragments in registers for the head) and runs
+// both products against each 16-query tile of the chunk; lane (c16, g) accumulates r_in[q] * max(P * dP, 0) for query c16 and
+// keys 4g .. 4g+3.  start 1 | 2: r_in is e_0 | 1/S (not read); with e_0 only query 0 contributes.
+constexpr int RKB = PM_WAVES * 16;   // keys per workgroup
+constexpr int RQC = 64;              // queries per staged chunk
+
+struct StepArgs {
+  const bf16* qkv;
+  const float* lse;
+  const bf16* dout;
+  const float* rin;
+  float* rout;
+  int S, H, nkb, start;
+  float scale_log2;
+};
 
 template <int DH>
+__global__ __launch_bounds__(PM_THREADS) void attn_relevance_step_kernel(StepArgs a) {
+  using Cf = PmCfg<DH>;
+  constexpr int KS = Cf::KS;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  bf16* Ks = reinterpret_cast<bf16*>(smem);
+  bf16* Vs = Ks + RKB * Cf::LD;
+  bf16* Qs = Vs + RKB * Cf::LD;
+  bf16* Ds = Qs + RQC * Cf::LD;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c16 = lane & 15, g = lane >> 4;
+  const int S = a.S, H = a.H, D = H * DH;
+  const long ldg = 3L * D;
+  const int b = blockIdx.x / a.nkb, k0 = (blockIdx.x - b * a.nkb) * RKB;
+  const int kc = min(RKB, S - k0);
+  const bool live = wave * 16 < kc;              // wave-uniform: this wave's key tile holds a key
+  const int qend = a.start == 1 ? 1 : S;         // r_in = e_0: query 0 alone
+  const bf16* fq = a.qkv + (long)b * S * ldg;
+  const bf16* fd = a.dout + (long)b * S * D;
+  const float* lse = a.lse + (long)b * H * S;
+  const float* rin = a.rin + (long)b * S;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  for (int h = 0; h < H; ++h) {
+    const bf16* hq = fq + h * DH;
+    bf16x8 kf[KS], vf[KS];
+    for (int q0 = 0; q0 < qend; q0 += RQC) {
+      if (q0 == 0) {
+        stage<DH>(Ks, hq + D, ldg, k0, RKB, S, tid);
+        stage<DH>(Vs, hq + 2 * D, ldg, k0, RKB, S, tid);
+      }
+      stage<DH>(Qs, hq, ldg, q0, RQC, S, tid);
+      stage<DH>(Ds, fd + h * DH, D, q0, RQC, S, tid);
+      __syncthreads();
+      if (live) {
+        if (q0 == 0) {
+#pragma unroll
+          for (int s = 0; s < KS; ++s) {
+            kf[s] = row_frag<DH>(Ks, wave * 16 + c16, s, lane);
+            vf[s] = row_frag<DH>(Vs, wave * 16 + c16, s, lane);
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < RQC / 16; ++u) {
+          if (q0 + u * 16 >= qend) break;         // wave-uniform
+          const int q = q0 + u * 16 + c16;
+          const bool qv = q < qend;
+          const float lq = qv ? lse[(long)h * S + q] * LOG2E : 0.f;
+          const float rq = !qv ? 0.f : a.start == 0 ? rin[q] : a.start == 1 ? 1.f : 1.0f / S;
+          f32x4 sc = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int s = 0; s < KS; ++s) {
+            const bf16x8 qf = row_frag<DH>(Qs, u * 16 + c16, s, lane);
+            const bf16x8 df = row_frag<DH>(Ds, u * 16 + c16, s, lane);
+            sc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[s], qf, sc, 0, 0, 0);
+            dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf[s], df, dp, 0, 0, 0);
+          }
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float p = fast_exp2(sc[r] * a.scale_log2 - lq);
+            const float gv = k0 + wave * 16 + 4 * g + r < S && qv ? fmaxf(p * dp[r], 0.f) : 0.f;
+            acc[r] += rq * gv;
+          }
+        }
+      }
+      __syncthreads();                           // Qs / Ds (and at the next head Ks / Vs) free
+    }
+  }
+  // sum over the 16 query lanes of each key (fixed butterfly), then r_out = r_in + acc / H
+#pragma unroll
+  for (int m = 1; m < 16; m <<= 1)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) acc[r] += __shfl_xor(acc[r], m);
+  if (live && c16 == 0) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int k = k0 + wave * 16 + 4 * g + r;
+      if (k < S) {
+        const float rk = a.start == 0 ? rin[k] : a.start == 1 ? (k == 0 ? 1.f : 0.f) : 1.0f / S;
+        a.rout[(long)b * S + k] = rk + acc[r] * (1.0f / H);
+      }
+    }
+  }
+}
+
+template <int DH> size_t probs_lds() { return (size_t)QB * PmCfg<DH>::LD * 2 + (size_t)KC * PmCfg<DH>::LD * 2 + (size_t)QB * PLD * 4; }
+
+template <int DH, bool GRAD>
 int launch_probs(const ProbsArgs& a, int B, hipStream_t st) {
   const size_t lds = probs_lds<DH>();
   // per frame where the forward runs its per-frame kernel (short sequences); else per (frame, head, query block), with the
@@ -310,8 +472,22 @@ int launch_probs(const ProbsArgs& a, int B, hipStream_t st) {
     g.nhg = (a.heads == 1 || frame) ? 1 : a.H;
     g.nqg = 1;
   }
-  (void)hipFuncSetAttribute((const void*)attn_probs_kernel<DH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  attn_probs_kernel<DH><<<(unsigned)((long)B * g.nhg * g.nqg), PM_THREADS, lds, st>>>(g);
+  const unsigned grid = (unsigned)((long)B * g.nhg * g.nqg);
+  if (GRAD) {
+    (void)hipFuncSetAttribute((const void*)attn_grad_probs_kernel<DH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    attn_grad_probs_kernel<DH><<<grid, PM_THREADS, lds, st>>>(g);
+  } else {
+    (void)hipFuncSetAttribute((const void*)attn_probs_kernel<DH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    attn_probs_kernel<DH><<<grid, PM_THREADS, lds, st>>>(g);
+  }
+  return iq_launch_status();
+}
+
+template <int DH>
+int launch_step(const StepArgs& a, int B, hipStream_t st) {
+  const size_t lds = (size_t)(2 * RKB + 2 * RQC) * PmCfg<DH>::LD * 2;
+  (void)hipFuncSetAttribute((const void*)attn_relevance_step_kernel<DH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  attn_relevance_step_kernel<DH><<<(unsigned)((long)B * a.nkb), PM_THREADS, lds, st>>>(a);
   return iq_launch_status();
 }
 
@@ -343,11 +519,73 @@ extern "C" int iq_attn_probs(const void* qkv, const float* lse, float* out, long
   a.qkv = (const bf16*)qkv; a.lse = lse; a.out = out; a.bstride = out_bstride;
   a.S = S; a.H = H; a.rows = rows; a.heads = heads; a.nhg = 1; a.nqg = 1;
   a.scale_log2 = LOG2E / sqrtf((float)dh);
+  a.dout = nullptr; a.positive = 0;
   switch (dh) {
-    case 16: return launch_probs<16>(a, B, st);
-    case 32: return launch_probs<32>(a, B, st);
-    default: return launch_probs<64>(a, B, st);
+    case 16: return launch_probs<16, false>(a, B, st);
+    case 32: return launch_probs<32, false>(a, B, st);
+    default: return launch_probs<64, false>(a, B, st);
   }
+}
+
+extern "C" int iq_attn_grad_probs(const void* qkv, const float* lse, const void* dout, float* out, long out_bstride, int B, int S,
+                                  int H, int dh, int rows, int heads, int positive, iq_stream_t stream) {
+  if (B < 0 || H <= 0 || rows < 0 || rows > 2 || heads < 0 || heads > 1 || positive < 0 || positive > 1) return IQ_ERR_ARG;
+  if (!iq_attn_supported(S, dh)) return IQ_ERR_UNSUPPORTED;
+  if (B == 0) return IQ_OK;
+  if (!qkv || !lse || !dout || !out || ((uintptr_t)qkv & 15) || ((uintptr_t)dout & 15) || ((uintptr_t)out & 3)) return IQ_ERR_ARG;
+  if (out_bstride < (long)(heads ? 1 : H) * S * (rows == 0 ? S : 1)) return IQ_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  IQ_PROF(IQ_FAM_MISC, st);
+  {
+    const double qrows = rows == 1 ? 1.0 : (double)S;
+    const double outb = 4.0 * B * (heads ? 1 : H) * (rows == 0 ? (double)S * S : (double)S);
+    IQ_PROF_K(2.0 * B * S * 3.0 * H * dh + 2.0 * B * qrows * H * dh + 4.0 * B * H * S + outb, 4.0 * B * H * qrows * S * dh,
+              "attn_grad_probs_kernel<%d>", dh);
+  }
+  ProbsArgs a;
+  a.qkv = (const bf16*)qkv; a.lse = lse; a.out = out; a.bstride = out_bstride;
+  a.S = S; a.H = H; a.rows = rows; a.heads = heads; a.nhg = 1; a.nqg = 1;
+  a.scale_log2 = LOG2E / sqrtf((float)dh);
+  a.dout = (const bf16*)dout; a.positive = positive;
+  switch (dh) {
+    case 16: return launch_probs<16, true>(a, B, st);
+    case 32: return launch_probs<32, true>(a, B, st);
+    default: return launch_probs<64, true>(a, B, st);
+  }
+}
+
+int attn_relevance_step_launch(const void* qkv, const float* lse, const void* dout, const float* r_in, float* r_out, int B, int S,
+                               int H, int dh, int start, hipStream_t st) {
+  if (B <= 0) return IQ_OK;
+  if (!iq_attn_supported(S, dh)) return IQ_ERR_UNSUPPORTED;
+  IQ_PROF(IQ_FAM_MISC, st);
+  {
+    const double qrows = start == 1 ? 1.0 : (double)S;
+    IQ_PROF_K(2.0 * B * S * 3.0 * H * dh + 2.0 * B * qrows * H * dh + 4.0 * B * H * qrows + 4.0 * B * (qrows + 2.0 * S),
+              4.0 * B * H * qrows * S * dh, "attn_relevance_step_kernel<%d>", dh);
+  }
+  StepArgs a;
+  a.qkv = (const bf16*)qkv; a.lse = lse; a.dout = (const bf16*)dout; a.rin = r_in; a.rout = r_out;
+  a.S = S; a.H = H; a.nkb = (S + RKB - 1) / RKB; a.start = start;
+  a.scale_log2 = LOG2E / sqrtf((float)dh);
+  switch (dh) {
+    case 16: return launch_step<16>(a, B, st);
+    case 32: return launch_step<32>(a, B, st);
+    default: return launch_step<64>(a, B, st);
+  }
+}
+
+extern "C" int iq_attn_relevance_step(const void* qkv, const float* lse, const void* dout, const float* r_in, float* r_out, int B,
+                                      int S, int H, int dh, iq_stream_t stream) {
+  if (B < 0 || H <= 0) return IQ_ERR_ARG;
+  if (!iq_attn_supported(S, dh)) return IQ_ERR_UNSUPPORTED;
+  if (B == 0) return IQ_OK;
+  if (!qkv || !lse || !dout || !r_in || !r_out || ((uintptr_t)qkv & 15) || ((uintptr_t)dout & 15) || ((uintptr_t)r_in & 3) ||
+      ((uintptr_t)r_out & 3))
+    return IQ_ERR_ARG;
+  const uintptr_t n = (uintptr_t)B * S * 4, i = (uintptr_t)r_in, o = (uintptr_t)r_out;
+  if (i < o + n && o < i + n) return IQ_ERR_ARG;          // r_out is written while other workgroups still read r_in
+  return attn_relevance_step_launch(qkv, lse, dout, r_in, r_out, B, S, H, dh, 0, (hipStream_t)stream);
 }
 
 int attn_rollout_launch(const unsigned char* qkv0, long qkv_lstride, const unsigned char* lse0, long lse_lstride, int L,

@@ -121,6 +121,23 @@ __global__ __launch_bounds__(256) void transpose_table_kernel(const float* __res
   }
 }
 
+// the relevance start vector: e_0 (cls) or 1/S per frame
+__global__ void rel_start_kernel(float* r, int n, int S, int cls) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const int k = i % S;
+    r[i] = cls ? (k == 0 ? 1.f : 0.f) : 1.0f / S;
+  }
+}
+
+// What iq_model_attention_relevance reads out of the data-only backward as each layer's attention-output gradient appears.
+struct RelHook {
+  float* const* maps;   // per layer or NULL
+  int rows, heads, positive;
+  long bstride;
+  float* rel;           // final relevance or NULL
+  float* r[2];          // ping-pong of the running relevance (the embedding-gradient rows, unused above layer 0)
+};
+
 __global__ void set_u32_kernel(uint32_t* p, uint32_t v, int bump) {
   if (threadIdx.x == 0 && blockIdx.x == 0) *p = bump ? *p + 1u : v;
 }
@@ -650,7 +667,8 @@ extern "C" int iq_model_grad_range(const iq_model_t* m, int stage_hi, int stage_
 // LayerNorm reduce, the CLS gradient, the embedding weight gradient); nothing is read from or written to m->grads.  The data
 // chain never reads what a weight-gradient launch writes, so its bits do not depend on pgrads.
 static int backward_impl(iq_model_t* m, const float* dlogits, const float* denc, int batch, void* workspace, size_t ws_bytes,
-                         int accumulate, int stage_hi, int stage_lo, bool pgrads, iq_stream_t stream) {
+                         int accumulate, int stage_hi, int stage_lo, bool pgrads, iq_stream_t stream,
+                         const RelHook* rh = nullptr) {
   if (!m->params || (pgrads && !m->grads) || !m->shadow) return fail(m, IQ_ERR_ARG, "backward: model not bound (grads required)");
   if (!workspace || batch <= 0) return fail(m, IQ_ERR_ARG, "backward: bad arguments");
   const iq_model_cfg_t& c = m->c;
@@ -757,6 +775,20 @@ static int backward_impl(iq_model_t* m, const float* dlogits, const float* denc,
       }
     }
     if (!post) IQ_TRY(iq_gemm_bf16_nt(dAo, D, m->sht(o.t_wo), D, ws + w.gAtt, D, M, D, D, nullptr, stream), "out-proj dgrad");
+    if (rh) {
+      // gAtt = d y / d (layer l's attention-core output): its gradient-weighted map and relevance step; below layer 0's
+      // attention nothing is needed
+      const float* lse = (const float*)(ws + a.lse);
+      if (rh->maps && rh->maps[l])
+        IQ_TRY(iq_attn_grad_probs(ws + a.qkv, lse, ws + w.gAtt, rh->maps[l], rh->bstride, B, S, H, m->dh, rh->rows, rh->heads,
+                                  rh->positive, stream), "gradient-weighted attention map");
+      if (rh->rel) {
+        const int i = Lr - 1 - l;
+        IQ_TRY(attn_relevance_step_launch(ws + a.qkv, lse, ws + w.gAtt, i ? rh->r[(i - 1) & 1] : nullptr, l ? rh->r[i & 1] : rh->rel,
+                                          B, S, H, m->dh, i ? 0 : m->has_cls ? 1 : 2, st), "relevance step");
+      }
+      if (l == 0) break;
+    }
     IQ_TRY(iq_attn_bwd(ws + a.qkv, ws + a.att, ws + w.gAtt, (const float*)(ws + a.lse), gQKV, B, S, H, m->dh, stream), "attention bwd");
     // The four weight gradients of the layer, BEFORE the QKV data gradient: fused with the norm2 backward of the layer
     // below, that GEMM overwrites gZ / gY and the norm2 partial rows, which the weight gradients / their reduce still read.
@@ -825,4 +857,35 @@ extern "C" int iq_model_backward_input(iq_model_t* m, const float* dlogits, cons
   IQ_TRY(iq_embed_dgrad(ws + w.demb, m->shadow + m->sh_embw, m->Ppad, dsrc, kind, batch, c.in_channels, H, W, p, c.d_model, stream),
          "embedding data gradient");
   return IQ_OK;
+}
+
+extern "C" int iq_model_attention_relevance(iq_model_t* m, const float* dlogits, int batch, void* workspace, size_t ws_bytes,
+                                            float* rel, float* const* maps, int rows, int heads, int positive, long out_bstride,
+                                            iq_stream_t stream) {
+  if (!m) return IQ_ERR_ARG;
+  if (!m->params || !m->shadow || !m->pe) return fail(m, IQ_ERR_ARG, "attention relevance: model not bound");
+  if (!dlogits) return fail(m, IQ_ERR_ARG, "attention relevance: dlogits is NULL");
+  WsPlan w;
+  const int rc = maps_check(m, workspace, ws_bytes, batch, "attention relevance", &w);
+  if (rc != IQ_OK) return rc;
+  if (rows < 0 || rows > 2 || heads < 0 || heads > 1)
+    return fail(m, IQ_ERR_ARG, "attention relevance: rows must be 0, 1 or 2 and heads 0 or 1");
+  if (positive < 0 || positive > 1) return fail(m, IQ_ERR_ARG, "attention relevance: positive must be 0 or 1");
+  const int L = m->c.n_layers, S = m->S, H = m->c.n_head;
+  bool any_map = false;
+  for (int l = 0; maps && l < L; ++l) any_map = any_map || maps[l];
+  if (!rel && !any_map) return fail(m, IQ_ERR_ARG, "attention relevance: rel and every map are NULL");
+  if (any_map && out_bstride < (long)(heads ? 1 : H) * S * (rows == 0 ? S : 1))
+    return fail(m, IQ_ERR_ARG, "attention relevance: out_bstride too small");
+  RelHook h;
+  h.maps = maps; h.rows = rows; h.heads = heads; h.positive = positive; h.bstride = out_bstride; h.rel = rel;
+  h.r[0] = (float*)((unsigned char*)workspace + w.demb);
+  h.r[1] = h.r[0] + (size_t)batch * S;
+  if (2 * (size_t)batch * S * sizeof(float) > (size_t)batch * m->tok * m->c.d_model * 2)     // (d_model >= 16 always fits)
+    return fail(m, IQ_ERR_UNSUPPORTED, "attention relevance: no room for the relevance vectors");
+  if (L == 0) {
+    if (rel) rel_start_kernel<<<blocks_for((size_t)batch * S), 256, 0, (hipStream_t)stream>>>(rel, batch * S, S, m->has_cls);
+    return iq_launch_status() == IQ_OK ? IQ_OK : fail(m, IQ_ERR_LAUNCH, "attention relevance: start vector launch failed");
+  }
+  return backward_impl(m, dlogits, nullptr, batch, workspace, ws_bytes, 0, L + 1, 1, false, stream, &h);
 }
