@@ -22,6 +22,11 @@
 // accumulator tiles hold and what tr_frag() fetches.
 // LDS images are [rows][dh+16] bf16 (32 B pad: conflict-free transposed reads, 2-way on row reads).
 // Softmax statistics fp32, exp2 domain.  dh in {16,32,64}; dh=16 zero-pads the QK^T contraction.
+//
+// Backward kernels: attn_bwd_once_kernel (dh = 64, no mask, padded length <= 224: the ViT shapes) forms S, P, dP and dS
+// once, in phase A, and hands dS to phase B's dQ product through an LDS image (5 MFMA products, 16 waves, one workgroup
+// per CU); attn_bwd_kernel (every other shape: masked, chunked, dh 16 / 32) recomputes them in phase B (7 products);
+// attn_frame_bwd_kernel takes short sequences one frame per workgroup.
 #include <stdlib.h>
 
 #include "common.h"
@@ -539,6 +544,226 @@ __global__ __launch_bounds__(ATT_THREADS, 4) void attn_bwd_kernel(const bf16* __
 }
 
 // ---------------------------------------------------------------------------------------------
+// backward, S x S terms computed ONCE (dh = 64, no mask, the whole sequence in one chunk: cfg B, S = 197)
+// ---------------------------------------------------------------------------------------------
+// attn_bwd_kernel's phase B rebuilds S^T, P, dP^T and dS from scratch (16 of its 24 MFMAs per 32 x 32 block, one exp2 and
+// ~10 VALU per score, a second fetch of V) only to feed dQ^T += K^T dS^T, although phase A held the same dS in registers.
+// Here phase A also writes every dS tile, rounded to bf16 exactly as pack_b rounds it for the dK product, into an LDS image
+// dS[query][key]; phase B is then four MFMAs per 16 queries and key block: K^T from tr_frag as before, the dS^T operand
+// two 8-byte row reads of the image (the lane's k-slots are keys {4g..4g+3} U {16+4g..16+4g+3} of query c16: the slot
+// order, the operands and the summation order of attn_bwd_kernel's dQ product -- no cross-wave reduction, no atomics).
+// LDS at S = 197: dS image 224 x (13 x 16 keys + 8 pad) bf16 = 96,768 B, which leaves room for Q / dO only as unpadded
+// 128-byte rows (2 x 28,672 B) + lse / delta 1,792 B = 155,904 B: one workgroup per CU, so it has NT / 64 = 16 waves
+// (phase A: the 13 key units in one pass; phase B: the 13 sixteen-query halves in one pass), capped at 128 VGPRs.
+// 128-byte rows are XOR-swizzled: the 32-byte column pair p of row r lives at pair p ^ ((r >> 1) & 3).  A 32-lane half of a
+// transposed read covers 8 consecutive rows x 32 B, of a row read 16 lanes cover 16 rows x 16 B: either way every 16-byte
+// slot of the 256-byte bank row exactly once (conflict-free; the padded 160-byte rows were 2-way on row reads).  The dS row
+// stride is 32 * nunit + 16 bytes = 4 * odd dwords: 16 queries x {g, g + 1} fill the 64 banks once.
+constexpr int ONCE_MAX_SPAD = 224;
+constexpr int ONCE_LD = 64;       // Q / dO / K image row stride (elements): no pad, swizzled
+
+__device__ __forceinline__ int once_off(int row, int col) { return row * ONCE_LD + (col ^ (((row >> 1) & 3) << 4)); }
+
+__device__ __forceinline__ bf16x8 once_tr_frag(const bf16* tile, int r0, int dt, int lane) {
+  const int i16 = lane & 15, g = lane >> 4;
+  const bf16* a = tile + once_off(r0 + 4 * g + (i16 >> 2), dt * 16 + 4 * (i16 & 3));
+  s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(a));
+  s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(a + 16 * ONCE_LD));   // row + 16: same swizzle
+  s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+  return __builtin_bit_cast(bf16x8, v);
+}
+__device__ __forceinline__ bf16x8 once_row_frag(const bf16* tile, int row, int s, int lane) {
+  return *reinterpret_cast<const bf16x8*>(tile + once_off(row, s * 32 + 8 * (lane >> 4)));
+}
+
+// rows [0, spad) of NIMG [S, 64] head slices -> swizzled images, rows >= S zero-filled; all loads of a trip requested
+// before the first write (see stage_pair)
+template <int NT, int UN, int NIMG>
+__device__ __forceinline__ void once_stage(bf16* const (&img)[NIMG], const bf16* const (&base)[NIMG],
+                                           const long (&ldg)[NIMG], int spad, int S, int tid) {
+  const int total = spad * 8;
+  for (int b0 = 0; b0 < total; b0 += UN * NT) {
+    bf16x8 v[NIMG][UN];
+#pragma unroll
+    for (int j = 0; j < UN; ++j) {
+      const int id = min(b0 + j * NT + tid, total - 1);
+      const int r = min(id >> 3, S - 1), c = id & 7;
+#pragma unroll
+      for (int i = 0; i < NIMG; ++i) v[i][j] = *reinterpret_cast<const bf16x8*>(base[i] + (long)r * ldg[i] + c * 8);
+    }
+#pragma unroll
+    for (int j = 0; j < UN; ++j) {
+      const int id = b0 + j * NT + tid;
+      const int r = id >> 3, c = id & 7;
+      if (id < total) {
+        const bool live = r < S;
+#pragma unroll
+        for (int i = 0; i < NIMG; ++i) *reinterpret_cast<bf16x8*>(img[i] + once_off(r, c * 8)) = live ? v[i][j] : bf16x8{};
+      }
+    }
+  }
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT, 4) void attn_bwd_once_kernel(const bf16* __restrict__ qkv, const bf16* __restrict__ out,
+                                                              const bf16* __restrict__ dout, const float* __restrict__ lse,
+                                                              bf16* __restrict__ dqkv, int S, int H, int spad, float scale) {
+  constexpr int DH = 64, KS = 2, DT = 4, NW = NT / 64;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  bf16* I0 = reinterpret_cast<bf16*>(smem);            // phase A: Q   | phase B: K
+  bf16* I1 = I0 + spad * ONCE_LD;                      // phase A: dO
+  float* lse_s = reinterpret_cast<float*>(I1 + spad * ONCE_LD);   // [spad], pre-multiplied by log2(e)
+  float* del_s = lse_s + spad;                                    // [spad]
+  bf16* dSi = reinterpret_cast<bf16*>(del_s + spad);              // [spad][ldS]: dS[query][key], bf16
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, c16 = lane & 15;
+  const int b = blockIdx.x / H, h = blockIdx.x % H;
+  const int D = H * DH;
+  const long ldg = 3L * D;
+  const bf16* qb = qkv + (long)b * S * ldg + h * DH;
+  const bf16* kb_ = qb + D;
+  const bf16* vb_ = qb + 2 * D;
+  const bf16* ob = out + (long)b * S * D + h * DH;
+  const bf16* dob = dout + (long)b * S * D + h * DH;
+  bf16* dqb = dqkv + (long)b * S * ldg + h * DH;
+  const float scale_log2 = scale * LOG2E;
+  const int nunit = (S + 15) / 16;      // 16-key units = 16-query halves that hold a real row
+  const int ldS = nunit * 16 + 8;
+
+  {
+    bf16* const img[2] = {I0, I1};
+    const bf16* const src[2] = {qb, dob};
+    const long lds_[2] = {ldg, (long)D};
+    once_stage<NT, 2048 / NT, 2>(img, src, lds_, spad, S, tid);
+  }
+  __syncthreads();
+  // delta from the dO image just staged; O comes from HBM, its only use (same order of summation as attn_bwd_kernel)
+  for (int q = tid; q < spad; q += NT) {
+    float dl = 0.f, ls = 0.f;
+    if (q < S) {
+#pragma unroll
+      for (int c = 0; c < 8; ++c) {
+        const bf16x8 a = *reinterpret_cast<const bf16x8*>(I1 + once_off(q, c * 8));
+        const bf16x8 o8 = *reinterpret_cast<const bf16x8*>(ob + (long)q * D + c * 8);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) dl += (float)a[e] * (float)o8[e];
+      }
+      ls = lse[((long)b * H + h) * S + q] * LOG2E;
+    }
+    del_s[q] = dl;
+    lse_s[q] = ls;
+  }
+  __syncthreads();
+
+  // ---- phase A: wave owns 16 keys, sweeps queries; dV^T, dK^T in registers, dS into the image --------------------
+  for (int unit = wave; unit < nunit; unit += NW) {       // wave-uniform
+    bf16x8 kf[KS], vf[KS];
+#pragma unroll
+    for (int s = 0; s < KS; ++s) {
+      kf[s] = row_frag_gmem<DH>(kb_, ldg, unit * 16 + c16, S, s, lane);
+      vf[s] = row_frag_gmem<DH>(vb_, ldg, unit * 16 + c16, S, s, lane);
+    }
+    f32x4 dv[DT], dk[DT];
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt) { dv[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; dk[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+    const int key = unit * 16 + c16;
+    const bool unit_partial = unit * 16 + 16 > S;         // wave-uniform
+    for (int ql = 0; ql < spad; ql += 32) {
+      const bool u1 = ql + 16 < S;        // wave-uniform: the block's second 16 queries are not all padding
+      f32x4 p[2], ds[2];   // [u]
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        if (u == 1 && !u1) { p[1] = f32x4{0.f, 0.f, 0.f, 0.f}; ds[1] = f32x4{0.f, 0.f, 0.f, 0.f}; continue; }
+        f32x4 sa = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int s = 0; s < KS; ++s) {
+          const bf16x8 qa = once_row_frag(I0, ql + u * 16 + c16, s, lane);
+          const bf16x8 da = once_row_frag(I1, ql + u * 16 + c16, s, lane);
+          sa = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa, kf[s], sa, 0, 0, 0);
+          dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(da, vf[s], dp, 0, 0, 0);
+        }
+        const f32x4 lq4 = *reinterpret_cast<const f32x4*>(lse_s + ql + u * 16 + 4 * g);
+        const f32x4 dl4 = *reinterpret_cast<const f32x4*>(del_s + ql + u * 16 + 4 * g);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          // Padded QUERY rows need no mask: Q = dO = 0 and lse = delta = 0 there, so P = 1 and dS = 0 (finite: phase B
+          // reads those image rows for lanes whose result is not stored).  Padded KEYS do (only this wave's unit can hold
+          // them): P = exp2(-lse) is unbounded when a row's scores are all very negative, and inf * 0 would poison dQ.
+          float pv = fast_exp2(sa[r] * scale_log2 - lq4[r]);
+          if (unit_partial) pv = key < S ? pv : 0.f;
+          p[u][r] = pv;
+          ds[u][r] = pv * (dp[r] - dl4[r]) * scale;
+        }
+      }
+      const bf16x8 pB = pack_b(p[0], p[1]), dsB = pack_b(ds[0], ds[1]);
+      // the image holds what the dK product consumes; a half of pure padding queries is never read back (its 16-query
+      // half index is >= nunit)
+      bf16* w = dSi + (ql + 4 * g) * ldS + key;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) w[r * ldS] = dsB[r];
+      if (u1) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) w[(16 + r) * ldS] = dsB[4 + r];
+      }
+#pragma unroll
+      for (int dt = 0; dt < DT; ++dt) {
+        const bf16x8 doT = once_tr_frag(I1, ql, dt, lane);
+        const bf16x8 qT = once_tr_frag(I0, ql, dt, lane);
+        dv[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(doT, pB, dv[dt], 0, 0, 0);
+        dk[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qT, dsB, dk[dt], 0, 0, 0);
+      }
+    }
+    if (key < S) {
+#pragma unroll
+      for (int dt = 0; dt < DT; ++dt) {
+        bf16x4 wk, wv;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { wk[r] = (bf16)dk[dt][r]; wv[r] = (bf16)dv[dt][r]; }
+        *reinterpret_cast<bf16x4*>(dqb + (long)key * ldg + D + dt * 16 + 4 * g) = wk;
+        *reinterpret_cast<bf16x4*>(dqb + (long)key * ldg + 2 * D + dt * 16 + 4 * g) = wv;
+      }
+    }
+  }
+
+  // ---- phase B: K over the Q image (rows >= S zero: tr_frag reads them); wave owns 16 queries, sweeps keys ---------
+  __syncthreads();
+  {
+    bf16* const img[1] = {I0};
+    const bf16* const src[1] = {kb_};
+    const long lds_[1] = {ldg};
+    once_stage<NT, 2048 / NT, 1>(img, src, lds_, spad, S, tid);
+  }
+  __syncthreads();
+  for (int half = wave; half < nunit; half += NW) {       // wave-uniform
+    const int q = half * 16 + c16;
+    const bf16* drow = dSi + q * ldS + 4 * g;
+    f32x4 dq[DT];
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt) dq[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int kl = 0; kl < spad; kl += 32) {
+      const bool k1 = kl + 16 < S;        // else the block's second 16 keys are padding no unit wrote: constant zero
+      const bf16x4 lo = *reinterpret_cast<const bf16x4*>(drow + kl);
+      bf16x4 hi = {};
+      if (k1) hi = *reinterpret_cast<const bf16x4*>(drow + kl + 16);
+      const bf16x8 dsB = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+#pragma unroll
+      for (int dt = 0; dt < DT; ++dt) {
+        const bf16x8 kT = once_tr_frag(I0, kl, dt, lane);
+        dq[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kT, dsB, dq[dt], 0, 0, 0);
+      }
+    }
+    if (q < S) {
+#pragma unroll
+      for (int dt = 0; dt < DT; ++dt) {
+        bf16x4 w;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) w[r] = (bf16)dq[dt][r];
+        *reinterpret_cast<bf16x4*>(dqb + (long)q * ldg + dt * 16 + 4 * g) = w;
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // Per-FRAME kernels for short sequences (cfg C: S = 65, 8 heads of 16)
 // ---------------------------------------------------------------------------------------------
 // One workgroup per (frame, head) is the wrong shape when S is a few 32-row tiles: at S = 65 the forward has 3 query tiles
@@ -1010,6 +1235,25 @@ int launch_bwd(const void* qkv, const void* out, const void* dout, const float* 
   return iq_launch_status();
 }
 
+// attn_bwd_once_kernel: dh = 64, no mask, padded length <= 224 rows (one chunk).  Returns its thread count, 0 = not its
+// shape.  IQ_TUNE_ATTN_BWD_ONCE=0|512|1024 turns it off / picks the workgroup size (probes; default 1024).
+inline int once_threads(int S, int dh, bool masked) {
+  static const int tune = [] { const char* e = getenv("IQ_TUNE_ATTN_BWD_ONCE"); return e ? atoi(e) : -1; }();
+  if (masked || dh != 64 || (S + 31) / 32 * 32 > ONCE_MAX_SPAD || tune == 0) return 0;
+  return tune == 512 ? 512 : 1024;
+}
+template <int NT>
+int launch_bwd_once(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int B, int S, int H,
+                    hipStream_t st) {
+  const int spad = (S + 31) / 32 * 32, nunit = (S + 15) / 16;
+  const size_t lds = (size_t)2 * spad * ONCE_LD * 2 + (size_t)2 * spad * sizeof(float) + (size_t)spad * (nunit * 16 + 8) * 2;
+  auto k = attn_bwd_once_kernel<NT>;
+  if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  k<<<B * H, NT, lds, st>>>((const bf16*)qkv, (const bf16*)out, (const bf16*)dout, lse, (bf16*)dqkv, S, H, spad,
+                            1.0f / sqrtf(64.0f));
+  return iq_launch_status();
+}
+
 template <bool MASKED>
 int dispatch_fwd(const void* qkv, void* out, float* lse, const uint8_t* mask, long hs, int B, int S, int H, int dh,
                  hipStream_t st) {
@@ -1074,9 +1318,11 @@ extern "C" int iq_attn_bwd_masked(const void* qkv, const void* out, const void* 
   hipStream_t st = (hipStream_t)stream;
   IQ_PROF(IQ_FAM_ATTN_BWD, st);
   const bool frame = !mask && (dh == 16 || dh == 32 || dh == 64) && use_frame(S, frame_bwd_lds(S, H, dh));
+  const int once = frame ? 0 : once_threads(S, dh, mask != nullptr);
   {
     const double rows = (double)B * S, Dm = (double)H * dh;      // qkv, out, dout read; dqkv written; 7 MFMA products
     if (frame) IQ_PROF_K(2.0 * rows * 8.0 * Dm + 4.0 * B * H * S, 14.0 * B * H * (double)S * S * dh, "attn_frame_bwd_kernel<%d>", dh);
+    else if (once) IQ_PROF_K(2.0 * rows * 8.0 * Dm + 4.0 * B * H * S, 10.0 * B * H * (double)S * S * dh, "attn_bwd_once_kernel<%d>", once);   // 5 products
     else IQ_PROF_K(2.0 * rows * 8.0 * Dm + 4.0 * B * H * S, 14.0 * B * H * (double)S * S * dh, "attn_bwd_kernel<%d, %s>", dh, mask ? "true" : "false");
   }
   if (frame) {
@@ -1086,6 +1332,8 @@ extern "C" int iq_attn_bwd_masked(const void* qkv, const void* out, const void* 
       default: return launch_frame_bwd<64>(qkv, out, dout, lse, dqkv, B, S, H, st);
     }
   }
+  if (once == 512) return launch_bwd_once<512>(qkv, out, dout, lse, dqkv, B, S, H, st);
+  if (once) return launch_bwd_once<1024>(qkv, out, dout, lse, dqkv, B, S, H, st);
   return mask ? dispatch_bwd<true>(qkv, out, dout, lse, dqkv, mask, mask_hstride, B, S, H, dh, st)
               : dispatch_bwd<false>(qkv, out, dout, lse, dqkv, nullptr, 0, B, S, H, dh, st);
 }
