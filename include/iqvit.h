@@ -34,6 +34,11 @@ typedef struct iq_dropout {
   float p;
   const uint32_t* step_dev; /* optional DEVICE u32 overriding `step` (bumped on device under hipGraph replay) */
 } iq_dropout_t;
+/* Dropout sites of the model plan are 0 (embedding) and 1 + 3*l, 2 + 3*l, 3 + 3*l of encoder layer l (csrc/model.hip); a
+ * caller of a single kernel may pass any other small id.  The top value of the word is RESERVED: it is the `site` counter word
+ * of the channel impairments below, so no dropout site may use it (a dropout stream with the same seed and step would repeat
+ * the impairment's bits). */
+#define IQ_SITE_IMPAIR 0xFFFFFFFFu
 
 /* ---------------------------------------------------------------------------------------
  * LayerNorm.  Replaces LayerNorm.forward, V/models/layers/layers_norm.py:11-19 (eps 1e-12,
@@ -268,6 +273,36 @@ int iq_attn_relevance_step(const void* qkv, const float* lse, const void* dout, 
  * CPU preprocessing (IEEE subtract and divide). */
 int iq_frames_preprocess(const float* raw, float* out, int n_frames, int len, int take, const float* stats,
                          iq_stream_t stream);
+/* Channel impairments in front of that pipeline, one launch (csrc/impair.hip): training augmentation (rotation, flip and noise
+ * of I/Q frames: Huang et al. 2019, "Data augmentation for deep learning-based radio modulation classification") and the
+ * physical axes of a robustness curve.  raw, out, take and stats are those of iq_frames_preprocess.  Per frame, in this order:
+ *   circular shift, conjugate, rotate sample n (the OUTPUT index) by theta + k*pi/2 + 2*pi*f*n, gain, add noise, z-score, layout.
+ * Noise: P = mean |s|^2 over all `len` samples after the gain; sigma^2 = P / 10^(snr/10) is the total noise power, I and Q
+ * get sigma^2 / 2 each (Box-Muller on uniforms in (0,1]).
+ * Random numbers: philox4x32 (7 rounds, csrc/common.h), key = seed (high word ^ high word of the frame index), counter =
+ * (c, low word of the frame index frame_base + i, IQ_SITE_IMPAIR, step).  c = 0xFFFFFFFF yields the frame's parameters; c = p
+ * yields the noise of output samples 2p and 2p+1.  Frame j's result therefore depends on neither n_frames nor how a set of
+ * frames is cut into calls.
+ * drawn: NULL or fp32 [n_frames, 8] = {theta, f, k, conj, s, g, snr_db, sigma per component}: the values the kernel used
+ * (snr_db NaN and sigma 0 without noise).
+ * With every range [0,0], rot90 = conj = shift_max = 0, gain 0 dB and SNR NaN the output is bit-identical to
+ * iq_frames_preprocess.
+ * IQ_STATUS_ARG before any launch: NULL raw / out / stats / imp, lo > hi, a non-finite bound (other than both SNR bounds NaN =
+ * no noise), rot90 / conj outside {0,1}, shift_max < 0 or >= len, take > len.  IQ_STATUS_UNSUPPORTED: len * 8 bytes above
+ * 64 KB (one workgroup keeps one frame in LDS). */
+typedef struct iq_impair {
+  float phase_lo, phase_hi;      /* carrier phase theta ~ U[lo,hi] rad */
+  float cfo_lo, cfo_hi;          /* frequency offset f ~ U[lo,hi] cycles/sample */
+  int   rot90;                   /* 1: add k*pi/2, k uniform in 0..3 */
+  int   conj;                    /* 1: Q -> -Q with probability 1/2 (before the rotation) */
+  int   shift_max;               /* circular time shift s uniform in 0..shift_max: out[n] = in[(n+s) % len] */
+  float gain_db_lo, gain_db_hi;  /* amplitude gain g = 10^(dB/20), dB ~ U[lo,hi] */
+  float snr_db_lo, snr_db_hi;    /* complex AWGN at SNR ~ U[lo,hi] dB relative to the power of the frame AS GIVEN (after gain) */
+  uint64_t seed; uint32_t step;  /* Philox key / counter word, as in iq_dropout_t */
+  uint64_t frame_base;           /* index of frame 0 of this call in the caller's stream of frames */
+} iq_impair_t;
+int iq_frames_impair(const float* raw, float* out, float* drawn, int n_frames, int len, int take, const float* stats,
+                     const iq_impair_t* imp, iq_stream_t stream);
 int iq_patchify(const float* src, void* patches, int kind, int B, int C, int H, int W, int p, int Kpad,
                 iq_stream_t stream);
 int iq_cls_rows(const float* cls, const float* pe, void* x0, int B, int S, int D, const iq_dropout_t* drop,

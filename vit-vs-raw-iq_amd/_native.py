@@ -25,6 +25,13 @@ class Dropout(C.Structure):
                 ("step_dev", C.c_void_p)]
 
 
+class Impair(C.Structure):
+    _fields_ = [("phase_lo", C.c_float), ("phase_hi", C.c_float), ("cfo_lo", C.c_float), ("cfo_hi", C.c_float),
+                ("rot90", C.c_int), ("conj", C.c_int), ("shift_max", C.c_int), ("gain_db_lo", C.c_float),
+                ("gain_db_hi", C.c_float), ("snr_db_lo", C.c_float), ("snr_db_hi", C.c_float), ("seed", C.c_uint64),
+                ("step", C.c_uint32), ("frame_base", C.c_uint64)]
+
+
 class Epilogue(C.Structure):
     _fields_ = [("bias", C.c_void_p), ("relu", C.c_int), ("pe", C.c_void_p), ("tok", C.c_int), ("seq", C.c_int),
                 ("cls_off", C.c_int), ("drop", Dropout), ("gate", C.c_void_p), ("ldg", C.c_int),
@@ -88,6 +95,7 @@ SIGNATURES = {
     "iq_attn_grad_probs": (_I, [_P, _P, _P, _P, C.c_long, _I, _I, _I, _I, _I, _I, _I, _P]),
     "iq_attn_relevance_step": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "iq_frames_preprocess": (_I, [_P, _P, _I, _I, _I, C.POINTER(C.c_float), _P]),
+    "iq_frames_impair": (_I, [_P, _P, _P, _I, _I, _I, C.POINTER(C.c_float), C.POINTER(Impair), _P]),
     "iq_patchify": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "iq_cls_rows": (_I, [_P, _P, _P, _I, _I, _I, C.POINTER(Dropout), _P]),
     "iq_embed_bwd_gather": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, C.POINTER(Dropout), _I, _P]),

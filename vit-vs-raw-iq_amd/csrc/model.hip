@@ -301,6 +301,7 @@ inline int use_chain_pre(int M) {
     if (rc_ != IQ_OK) return fail(m, rc_, std::string(what) + " failed (status " + std::to_string(rc_) + ")"); \
   } while (0)
 
+// site ids: 0 = embedding, 1 + 3*l / 2 + 3*l / 3 + 3*l = layer l; IQ_SITE_IMPAIR (iqvit.h) is reserved for impair.hip
 iq_dropout_t site(const iq_model* m, uint64_t seed, const uint32_t* step_dev, uint32_t id, bool training) {
   iq_dropout_t d;
   d.seed = seed; d.step = 0; d.site = id; d.p = training ? m->c.drop_prob : 0.f; d.step_dev = step_dev;

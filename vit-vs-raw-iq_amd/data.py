@@ -190,9 +190,13 @@ class DeviceInputPipeline:
     (`pin_memory=True`, `.to(device, non_blocking=True)`, V/training/train.py:351-364,189-190).  Here the RAW
     `(B, len, 2)` fp32 frames go into one of two pinned staging buffers, cross PCIe on a copy stream while the previous
     step computes, and `iq_frames_preprocess` produces the `(B,1,H,W)` ViT image or the `(B,2,len)` raw-IQ tensor on
-    the compute stream.  No CPU fallback: construction fails without the HIP library / a GPU."""
+    the compute stream.  With `augment` (an impairments.Impairments, e.g. Impairments.augmentation()) the same launch slot
+    runs `iq_frames_impair` instead: every `get()` draws fresh channel impairments keyed by (`seed`, step = the number of
+    earlier `get()` calls or `get(step=...)`, frame index in the batch).  No CPU fallback: construction fails without the HIP
+    library / a GPU."""
 
-    def __init__(self, stats: dict, layout: str, batch: int, length: int = 1024, h: int = 32, w: int = 64, device="cuda"):
+    def __init__(self, stats: dict, layout: str, batch: int, length: int = 1024, h: int = 32, w: int = 64, device="cuda",
+                 augment=None, seed: int = 0):
         import ctypes as C
         import torch
         from . import _native as N
@@ -207,6 +211,14 @@ class DeviceInputPipeline:
         if self.device.type != "cuda":
             raise N.IqError("DeviceInputPipeline needs a CUDA/HIP device (no CPU fallback)")
         self._stats = (C.c_float * 4)(stats["i_mean"], stats["i_std"], stats["q_mean"], stats["q_std"])
+        if augment is not None:
+            from .impairments import Impairments
+            if not isinstance(augment, Impairments):
+                raise TypeError(f"augment must be an Impairments or None, got {type(augment).__name__}")
+            if augment.shift_max >= length:
+                raise ValueError(f"augment.shift_max {augment.shift_max} must be below the frame length {length}")
+            augment.struct(seed, 0, 0)                    # validates the seed
+        self._augment, self._seed, self._calls = augment, seed, 0
         self._host = [torch.empty(batch, length, 2, dtype=torch.float32).pin_memory() for _ in range(2)]
         self._dev = [torch.empty(batch, length, 2, dtype=torch.float32, device=self.device) for _ in range(2)]
         self._ready = [torch.cuda.Event(), torch.cuda.Event()]
@@ -228,8 +240,9 @@ class DeviceInputPipeline:
         self._pending = (s, n)
         self._slot ^= 1
 
-    def get(self):
-        """The submitted batch as the model's input tensor (on the current stream)."""
+    def get(self, step=None):
+        """The submitted batch as the model's input tensor (on the current stream).  `step` (augment only) overrides the
+        count of earlier get() calls as the step word of the random numbers."""
         torch = self._torch
         if self._pending is None:
             raise RuntimeError("get() without a submitted batch")
@@ -238,8 +251,15 @@ class DeviceInputPipeline:
         cur = torch.cuda.current_stream(self.device)
         cur.wait_event(self._ready[s])
         out = torch.empty(n, 2, self.take, dtype=torch.float32, device=self.device)
-        self._N.check(self._L.iq_frames_preprocess(self._dev[s].data_ptr(), out.data_ptr(), n, self.length, self.take,
-                                                   self._stats, cur.cuda_stream), "iq_frames_preprocess")
+        if self._augment is None:
+            self._N.check(self._L.iq_frames_preprocess(self._dev[s].data_ptr(), out.data_ptr(), n, self.length, self.take,
+                                                       self._stats, cur.cuda_stream), "iq_frames_preprocess")
+        else:
+            import ctypes as C
+            par = self._augment.struct(self._seed, self._calls & 0xFFFFFFFF if step is None else step, 0)
+            self._N.check(self._L.iq_frames_impair(self._dev[s].data_ptr(), out.data_ptr(), None, n, self.length, self.take,
+                                                   self._stats, C.byref(par), cur.cuda_stream), "iq_frames_impair")
+        self._calls += 1
         self._free[s].record(cur)
         return out.view(n, 1, self.h, self.w) if self.layout == "vit" else out
 
