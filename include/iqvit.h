@@ -39,6 +39,8 @@ typedef struct iq_dropout {
  * of the channel impairments below, so no dropout site may use it (a dropout stream with the same seed and step would repeat
  * the impairment's bits). */
 #define IQ_SITE_IMPAIR 0xFFFFFFFFu
+/* The value below it is RESERVED too: the `site` counter word of the synthetic frame source (iq_frames_synth). */
+#define IQ_SITE_SYNTH 0xFFFFFFFEu
 
 /* ---------------------------------------------------------------------------------------
  * LayerNorm.  Replaces LayerNorm.forward, V/models/layers/layers_norm.py:11-19 (eps 1e-12,
@@ -303,6 +305,49 @@ typedef struct iq_impair {
 } iq_impair_t;
 int iq_frames_impair(const float* raw, float* out, float* drawn, int n_frames, int len, int take, const float* stats,
                      const iq_impair_t* imp, iq_stream_t stream);
+/* Synthetic labelled frames made on the device (csrc/synth.hip): the transmitter in front of the channel above.  Frame j =
+ * frame_base + i of stream `stream` is a pure function of (seed, stream, j): it depends on neither n_frames nor how a set of
+ * frames is cut into calls.  The recipe is data.make_dataset's, 1 sample per symbol; per frame, in this order:
+ *   1. draw the symbols of the frame's class, 2. rotate every sample by one carrier phase theta ~ U[0, 2 pi),
+ *   3. divide by sqrt(mean |s|^2 + 1e-12) of that frame, 4. add complex AWGN, sigma = sqrt(0.5 * 10^(-snr/10)) per component.
+ * Class and SNR: balanced = 1: class = j % n_classes, SNR index = (j / n_classes) % n_snrs; balanced = 0: both drawn (below).
+ * Random numbers: philox4x32 (7 rounds, csrc/common.h), key = (low word of seed, high word of seed ^ high word of j), counter =
+ * (c, low word of j, IQ_SITE_SYNTH, stream).  A word w becomes an integer in [0, M) as (uint64(w) * M) >> 32 (no modulo).
+ *   c = 0xFFFFFFFF: the frame's parameters.  word 0: theta = fp32(2 pi) * (w >> 8) * 2^-24 (the rotation itself is
+ *                   sincospi(2 * (w >> 8) * 2^-24)); balanced = 0 only: word 1 -> class in [0, n_classes), word 2 -> SNR index
+ *                   in [0, n_snrs).  Word 3 is not used.
+ *   c = p < 0x80000000: words 4p .. 4p+3 of the frame's symbol stream; len + 2 words are used:
+ *       kind 0  sample n = points[offset + idx], idx = word n mapped to [0, count);                     symbols[n] = idx
+ *       kind 1  GMSK approximation: b_n = 2 * (word n & 1) - 1 for n = 0 .. len+1, m_n = b_n + 2 b_{n+1} + b_{n+2},
+ *               M_n = sum_{i <= n} m_i (int32), sample n = exp(j pi (M_n mod 16) / 8);                  symbols[n] = M_n mod 16
+ *       kind 2  OQPSK: t_k = word k & 1; I[n] = t_{n/2}, Q[n] = t_{K0 + (n+1)/2}, K0 = len/2 + 1 (integer divisions),
+ *               sample n = ((2 I - 1) + j (2 Q - 1)) / sqrt(2);                                         symbols[n] = 2 I + Q
+ *   c = 0x80000000 + p: the noise of samples 2p and 2p+1: (I, Q) of sample 2p from words (0, 1), of sample 2p+1 from words
+ *       (2, 3), each pair through Box-Muller on uniforms in (0,1] (the transform of iq_frames_impair):
+ *       r = sqrt(-2 log(((a >> 8) + 1) 2^-24)), (I, Q) = r * (cos, sin)(2 pi (b >> 8) 2^-24).
+ * Outputs: raw[n_frames, len, 2] fp32 (I, Q) pairs, the layout iq_frames_preprocess / iq_frames_impair read; labels[n_frames]
+ * the class index; snr[n_frames] the SNR in dB (NaN when n_snrs = 0: no noise); drawn: NULL or fp32 [n_frames, 4] = {class,
+ * snr_db, theta, mean |s|^2 before the normalisation}; symbols: NULL or int32 [n_frames, len] as listed above.
+ * IQ_STATUS_ARG before any launch: NULL raw / labels / snr / par / classes, n_classes <= 0, n_snrs < 0 or NULL snrs_db with
+ * n_snrs > 0, a kind outside 0..2, kind 0 with count <= 0, offset < 0 or NULL points, a non-finite SNR, balanced outside {0,1},
+ * len <= 0, a misaligned pointer.  IQ_STATUS_UNSUPPORTED: len * 8 bytes above 64 KB (one workgroup keeps one frame in LDS),
+ * more than IQ_SYNTH_MAX_CLASSES classes or IQ_SYNTH_MAX_SNRS SNR values (both tables travel in the kernel arguments). */
+#define IQ_SYNTH_MAX_CLASSES 128
+#define IQ_SYNTH_MAX_SNRS 64
+typedef struct iq_synth_class { int kind; int offset; int count; } iq_synth_class_t;
+    /* kind 0: memoryless constellation, points[offset .. offset+count)
+       kind 1: GMSK approximation; kind 2: OQPSK (offset / count ignored for 1, 2) */
+typedef struct iq_synth {
+  const float* points;            /* DEVICE fp32 (re, im) pairs, already scaled to unit mean power */
+  const iq_synth_class_t* classes; int n_classes;     /* HOST array, copied into the launch */
+  const float* snrs_db; int n_snrs;                    /* HOST array; n_snrs = 0: no noise */
+  int balanced;                   /* 1: class = j % K, SNR index = (j / K) % n_snrs (make_dataset's pattern); 0: both drawn */
+  uint64_t seed; uint32_t stream; /* Philox key / counter word 3: stream 0 = train, 1 = validation, ... disjoint frames */
+  uint64_t frame_base;            /* index j of frame 0 of this call */
+} iq_synth_t;
+int iq_frames_synth(float* raw /*[n,len,2]*/, int64_t* labels, float* snr /*[n], NaN when no noise*/,
+                    float* drawn /*NULL or [n,4] = {class, snr_db, phase, power before normalisation}*/,
+                    int32_t* symbols /*NULL or [n,len]*/, int n_frames, int len, const iq_synth_t* par, iq_stream_t stream);
 int iq_patchify(const float* src, void* patches, int kind, int B, int C, int H, int W, int p, int Kpad,
                 iq_stream_t stream);
 int iq_cls_rows(const float* cls, const float* pe, void* x0, int B, int S, int D, const iq_dropout_t* drop,

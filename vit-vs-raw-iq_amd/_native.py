@@ -32,6 +32,16 @@ class Impair(C.Structure):
                 ("step", C.c_uint32), ("frame_base", C.c_uint64)]
 
 
+class SynthClass(C.Structure):
+    _fields_ = [("kind", C.c_int), ("offset", C.c_int), ("count", C.c_int)]
+
+
+class Synth(C.Structure):
+    _fields_ = [("points", C.c_void_p), ("classes", C.POINTER(SynthClass)), ("n_classes", C.c_int),
+                ("snrs_db", C.POINTER(C.c_float)), ("n_snrs", C.c_int), ("balanced", C.c_int), ("seed", C.c_uint64),
+                ("stream", C.c_uint32), ("frame_base", C.c_uint64)]
+
+
 class Epilogue(C.Structure):
     _fields_ = [("bias", C.c_void_p), ("relu", C.c_int), ("pe", C.c_void_p), ("tok", C.c_int), ("seq", C.c_int),
                 ("cls_off", C.c_int), ("drop", Dropout), ("gate", C.c_void_p), ("ldg", C.c_int),
@@ -96,6 +106,7 @@ SIGNATURES = {
     "iq_attn_relevance_step": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "iq_frames_preprocess": (_I, [_P, _P, _I, _I, _I, C.POINTER(C.c_float), _P]),
     "iq_frames_impair": (_I, [_P, _P, _P, _I, _I, _I, C.POINTER(C.c_float), C.POINTER(Impair), _P]),
+    "iq_frames_synth": (_I, [_P, _P, _P, _P, _P, _I, _I, C.POINTER(Synth), _P]),
     "iq_patchify": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "iq_cls_rows": (_I, [_P, _P, _P, _I, _I, _I, C.POINTER(Dropout), _P]),
     "iq_embed_bwd_gather": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, C.POINTER(Dropout), _I, _P]),

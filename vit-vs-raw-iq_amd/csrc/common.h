@@ -80,6 +80,18 @@ __device__ __forceinline__ u32x4 philox4x32(uint32_t c0, uint32_t c1, uint32_t c
   return o;
 }
 
+// 24-bit uniforms of one Philox word and the Box-Muller transform of the noise generators (impair.hip, synth.hip)
+__device__ __forceinline__ float u24(uint32_t w) { return (float)(w >> 8) * 0x1p-24f; }                // [0, 1)
+__device__ __forceinline__ float u24_open(uint32_t w) { return (float)((w >> 8) + 1u) * 0x1p-24f; }    // (0, 1]: log() is finite
+// two independent N(0,1) from two words
+__device__ __forceinline__ void box_muller(uint32_t a, uint32_t b, float& g0, float& g1) {
+  const float r = sqrtf(-2.f * logf(u24_open(a)));
+  float sn, cs;
+  sincospif(2.f * u24(b), &sn, &cs);
+  g0 = r * cs;
+  g1 = r * sn;
+}
+
 // 8 keep-flags (bit i = element i of the group is kept)
 __device__ __forceinline__ uint32_t dropout_keep8(const IqRng& r, uint64_t group, uint32_t thresh) {
   u32x4 b = philox4x32((uint32_t)group, (uint32_t)(group >> 32), r.site, r.step,

@@ -36,18 +36,7 @@ struct ImpArgs {
   int st2;    // both channels of every output frame start 8-byte aligned (take even): float2 stores
 };
 
-__device__ __forceinline__ float u24(uint32_t w) { return (float)(w >> 8) * 0x1p-24f; }                // [0, 1)
-__device__ __forceinline__ float u24_open(uint32_t w) { return (float)((w >> 8) + 1u) * 0x1p-24f; }    // (0, 1]: log() is finite
 __device__ __forceinline__ float draw(float lo, float hi, float u) { return fminf(fmaxf(fmaf(hi - lo, u, lo), lo), hi); }
-
-// two independent N(0,1) from two words
-__device__ __forceinline__ void box_muller(uint32_t a, uint32_t b, float& g0, float& g1) {
-  const float r = sqrtf(-2.f * logf(u24_open(a)));
-  float sn, cs;
-  sincospif(2.f * u24(b), &sn, &cs);
-  g0 = r * cs;
-  g1 = r * sn;
-}
 
 template <bool NOISE>
 __global__ __launch_bounds__(IMP_THREADS) void frames_impair_kernel(ImpArgs a) {
