@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/iqvit.h"
+
 typedef __bf16 bf16;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
@@ -11,6 +13,9 @@ typedef __attribute__((ext_vector_type(4))) short s16x4;
 typedef __attribute__((ext_vector_type(8))) short s16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
+// operands of __builtin_amdgcn_global_load_lds (global -> LDS DMA)
+typedef __attribute__((address_space(3))) void lds_void_t;
+typedef __attribute__((address_space(1))) const void gbl_cvoid_t;
 
 #define IQ_OK 0
 #define IQ_ERR_ARG 1
@@ -116,6 +121,21 @@ __host__ __device__ inline float dropout_scale(float p) {
   uint32_t t = dropout_thresh(p);
   return 65536.0f / (65536.0f - (float)t);
 }
+
+// Host: a dropout site of the C ABI as the kernels take it.  Off (no site, or p <= 0) is (0, zero rng, 0, 1.f).
+// Returns false for p >= 1, which most entry points refuse; the outputs are filled either way (thresh clamps at 65535).
+inline bool dropout_unpack(const iq_dropout_t* d, int* on, IqRng* rng, uint32_t* thresh, float* dscale) {
+  *on = 0; *rng = IqRng{0, 0, 0, nullptr}; *thresh = 0; *dscale = 1.f;
+  if (!d || !(d->p > 0.f)) return true;
+  *on = 1;
+  *rng = IqRng{d->seed, d->step, d->site, d->step_dev};
+  *thresh = dropout_thresh(d->p);
+  *dscale = dropout_scale(d->p);
+  return d->p < 1.f;
+}
+
+// immediate of s_waitcnt for vmcnt(n), n < 64, every other counter left alone (gfx9 encoding: vmcnt in bits 3:0 and 15:14)
+constexpr int vmcnt_imm(int n) { return (n & 15) | ((n >> 4) << 14) | 0x0F70; }
 
 // bijective XCD-aware block remap (guide T1): consecutive logical tiles run on one XCD
 __device__ __forceinline__ int xcd_remap(int bid, int nwg) {

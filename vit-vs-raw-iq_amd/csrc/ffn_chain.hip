@@ -48,8 +48,6 @@
 namespace {
 
 constexpr int FC_CHUNK = 64, FC_NS = 3, FC_MAXW = 7;
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void gbl_cvoid_t;
 
 struct FfnChainParams {
   const bf16* X1; const bf16* W1; const bf16* W2;      // [M,D], [F,D], [D,F]
@@ -1270,19 +1268,8 @@ int chain_fwd(const ChainPre* pre, const void* X1, const void* W1, const float* 
   p.gate = (uint32_t*)gate_bits;
   if ((uintptr_t)gate_bits % 16) return IQ_ERR_ARG;
   p.M = frames * S; p.F = F; p.eps = eps;
-  auto fill = [](const iq_dropout_t* d, int* on, IqRng* r, uint32_t* th, float* sc) -> bool {
-    *on = 0; *th = 0; *sc = 1.f; *r = IqRng{0, 0, 0, nullptr};
-    if (d && d->p > 0.f) {
-      if (d->p >= 1.f) return false;
-      *on = 1;
-      r->seed = d->seed; r->step = d->step; r->site = d->site; r->step_dev = d->step_dev;
-      *th = dropout_thresh(d->p);
-      *sc = dropout_scale(d->p);
-    }
-    return true;
-  };
-  if (!fill(drop1, &p.drop1_on, &p.rng1, &p.thresh1, &p.dscale1) || !fill(drop2, &p.drop2_on, &p.rng2, &p.thresh2, &p.dscale2))
-    return IQ_ERR_ARG;
+  if (!dropout_unpack(drop1, &p.drop1_on, &p.rng1, &p.thresh1, &p.dscale1) ||
+      !dropout_unpack(drop2, &p.drop2_on, &p.rng2, &p.thresh2, &p.dscale2)) return IQ_ERR_ARG;
   if (pre) {
     if (!pre->A0 || !pre->W0 || !pre->b0 || !pre->R0 || !pre->gamma0 || !pre->beta0 || !pre->Z0 || !pre->mean0 || !pre->rstd0)
       return IQ_ERR_ARG;
@@ -1290,7 +1277,7 @@ int chain_fwd(const ChainPre* pre, const void* X1, const void* W1, const float* 
          (uintptr_t)pre->beta0 | (uintptr_t)pre->Z0) % 16) return IQ_ERR_ARG;
     p.A0 = (const bf16*)pre->A0; p.W0 = (const bf16*)pre->W0; p.R0 = (const bf16*)pre->R0; p.b0 = pre->b0;
     p.gamma0 = pre->gamma0; p.beta0 = pre->beta0; p.Z0 = (bf16*)pre->Z0; p.X1out = (bf16*)X1; p.mean0 = pre->mean0; p.rstd0 = pre->rstd0;
-    if (!fill(pre->drop0, &p.drop0_on, &p.rng0, &p.thresh0, &p.dscale0)) return IQ_ERR_ARG;
+    if (!dropout_unpack(pre->drop0, &p.drop0_on, &p.rng0, &p.thresh0, &p.dscale0)) return IQ_ERR_ARG;
     if (pre->Wq || pre->bq || pre->Yq) {
       if (!pre->Wq || !pre->bq || !pre->Yq || ((uintptr_t)pre->Wq | (uintptr_t)pre->bq | (uintptr_t)pre->Yq) % 16) return IQ_ERR_ARG;
       p.Wq = (const bf16*)pre->Wq; p.bq = pre->bq; p.Yq = (bf16*)pre->Yq;
@@ -1362,13 +1349,7 @@ int chain_bwd(const ChainBwdPre* pre, const void* dO, const void* W2t, const voi
   p.gH = (bf16*)gH; p.dZ = (bf16*)dz; p.dY = (bf16*)dy; p.partial = partial;
   p.M = frames * S; p.F = F; p.gate_scale = gate_scale;
   p.Wot = (const bf16*)Wot; p.dA = (bf16*)dA;
-  if (drop && drop->p > 0.f) {
-    if (drop->p >= 1.f || !dy) return IQ_ERR_ARG;
-    p.drop_on = 1;
-    p.rng.seed = drop->seed; p.rng.step = drop->step; p.rng.site = drop->site; p.rng.step_dev = drop->step_dev;
-    p.thresh = dropout_thresh(drop->p);
-    p.dscale = dropout_scale(drop->p);
-  }
+  if (!dropout_unpack(drop, &p.drop_on, &p.rng, &p.thresh, &p.dscale) || (p.drop_on && !dy)) return IQ_ERR_ARG;
   if (pre) {
     if (!Wot) return IQ_ERR_ARG;                        // (built with the last stage only)
     if (!pre->A0 || !pre->W0t || !pre->R0 || !pre->Z0 || !pre->mean0 || !pre->rstd0 || !pre->gamma0 || !pre->dZ0 || !pre->partial0)
@@ -1380,7 +1361,8 @@ int chain_bwd(const ChainBwdPre* pre, const void* dO, const void* W2t, const voi
     p.A0 = (const bf16*)pre->A0; p.W0t = (const bf16*)pre->W0t; p.R0 = (const bf16*)pre->R0; p.Z0 = (const bf16*)pre->Z0;
     p.mean0 = pre->mean0; p.rstd0 = pre->rstd0; p.gamma0 = pre->gamma0;
     p.dZ0 = (bf16*)pre->dZ0; p.dY0 = (bf16*)pre->dY0; p.partial0 = pre->partial0;
-    if (p.drop_on) { p.rng0.seed = pre->drop0->seed; p.rng0.step = pre->drop0->step; p.rng0.site = pre->drop0->site; p.rng0.step_dev = pre->drop0->step_dev; }
+    int on0; uint32_t thresh0; float dscale0;            // = those of `drop` (p0 == p1): the kernel takes only the site's rng
+    (void)dropout_unpack(pre->drop0, &on0, &p.rng0, &thresh0, &dscale0);
   }
   hipStream_t st = (hipStream_t)stream;
   IQ_PROF(IQ_FAM_GEMM_NT, st);

@@ -32,11 +32,8 @@
 namespace {
 
 constexpr int BG_THREADS = 512, BG_BM = 256, BG_BN = 256, BG_KT = 64, BG_UNIT = 128 * 128;   // unit: 128 rows x 128 B
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void gbl_cvoid_t;
 
 // s_waitcnt immediate that waits for vmcnt <= n only (gfx9 layout: vmcnt[3:0] | expcnt[6:4] | lgkmcnt[11:8] | vmcnt[5:4] << 14)
-constexpr int bg_vmcnt(int n) { return (n & 15) | ((n >> 4) << 14) | 0x0F70; }
 
 template <int EPI>
 __global__ __launch_bounds__(BG_THREADS, 1) void gemm_big_kernel(const GemmParams p, int ntiles) {
@@ -122,7 +119,7 @@ __global__ __launch_bounds__(BG_THREADS, 1) void gemm_big_kernel(const GemmParam
   issue_advance();
   issue_a(0); issue_b(0);
 
-  __builtin_amdgcn_s_waitcnt(bg_vmcnt(6));                       // A0, B0, B1 of K-tile 0 landed (A1, A0', B0' in flight)
+  __builtin_amdgcn_s_waitcnt(vmcnt_imm(6));                       // A0, B0, B1 of K-tile 0 landed (A1, A0', B0' in flight)
   __builtin_amdgcn_s_barrier();                                  // barrier 0
   if (wr == 1) __builtin_amdgcn_s_barrier();                     // half 1 runs one phase-half behind
 
@@ -154,10 +151,10 @@ __global__ __launch_bounds__(BG_THREADS, 1) void gemm_big_kernel(const GemmParam
   auto sync_a = [&](int left) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     if (wr == 1) {
-      if (left == 8) __builtin_amdgcn_s_waitcnt(bg_vmcnt(8));
-      else if (left == 6) __builtin_amdgcn_s_waitcnt(bg_vmcnt(6));
-      else if (left == 2) __builtin_amdgcn_s_waitcnt(bg_vmcnt(2));
-      else if (left == 0) __builtin_amdgcn_s_waitcnt(bg_vmcnt(0));
+      if (left == 8) __builtin_amdgcn_s_waitcnt(vmcnt_imm(8));
+      else if (left == 6) __builtin_amdgcn_s_waitcnt(vmcnt_imm(6));
+      else if (left == 2) __builtin_amdgcn_s_waitcnt(vmcnt_imm(2));
+      else if (left == 0) __builtin_amdgcn_s_waitcnt(vmcnt_imm(0));
     }
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
@@ -165,10 +162,10 @@ __global__ __launch_bounds__(BG_THREADS, 1) void gemm_big_kernel(const GemmParam
   };
   auto sync_b = [&](int left) {
     if (wr == 0) {
-      if (left == 8) __builtin_amdgcn_s_waitcnt(bg_vmcnt(8));
-      else if (left == 6) __builtin_amdgcn_s_waitcnt(bg_vmcnt(6));
-      else if (left == 2) __builtin_amdgcn_s_waitcnt(bg_vmcnt(2));
-      else if (left == 0) __builtin_amdgcn_s_waitcnt(bg_vmcnt(0));
+      if (left == 8) __builtin_amdgcn_s_waitcnt(vmcnt_imm(8));
+      else if (left == 6) __builtin_amdgcn_s_waitcnt(vmcnt_imm(6));
+      else if (left == 2) __builtin_amdgcn_s_waitcnt(vmcnt_imm(2));
+      else if (left == 0) __builtin_amdgcn_s_waitcnt(vmcnt_imm(0));
     }
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
@@ -230,7 +227,7 @@ __global__ __launch_bounds__(BG_THREADS, 1) void gemm_big_kernel(const GemmParam
       EpiRegs<MT, NT, EPI> R;
       R.rng = rng;
       epi_load_early<MT, NT, EPI>(p, R, row0, col0, lane);
-      __builtin_amdgcn_s_waitcnt(bg_vmcnt(0));
+      __builtin_amdgcn_s_waitcnt(vmcnt_imm(0));
       epi_finish<MT, NT, EPI>(p, acc, R, row0, col0, lane);
     }
     lane_offsets();

@@ -10,7 +10,7 @@
 // and cost a launch; here the row statistics come from the tile that is already in registers.
 //
 // Whole-row tile: one workgroup owns BMT rows x all D columns (D = BN in {128, 192, 256}), 4 waves as 2 (rows) x 2
-// (column halves).  Main loop = the global_load_lds ring of gemm_nt.hip (3 slots, 32-deep stages, counted vmcnt, raw
+// (column halves).  Main loop = the global_load_lds ring of gemm_nt.hip / gemm_ring.h (3 slots, 32-deep stages, counted vmcnt, raw
 // s_barrier).  The tail's global loads (bias, residual rows) are issued when the LAST operand stage has been issued,
 // so they travel under the last two stages' MFMAs instead of being exposed after the loop (they are the youngest
 // entries of the in-order vmcnt queue, so the stage waits simply leave them outstanding).
@@ -21,14 +21,13 @@
 
 #include "common.h"
 #include "gemm_common.h"
+#include "gemm_ring.h"
 #include "iqvit.h"
 #include "prof.h"
 
 namespace {
 
 constexpr int LNG_THREADS = 256;
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void gbl_cvoid_t;
 
 struct GemmLnParams {
   const bf16* A; const bf16* B;            // [M,K], [D,K]
@@ -42,18 +41,12 @@ struct GemmLnParams {
   float eps;
 };
 
-__device__ __forceinline__ int lswz64(int row) { return (0x78 >> (((row >> 2) & 3) * 2)) & 3; }   // {0,2,3,1}: gemm_nt.hip
-
 template <int BMT, int BN>
 __global__ __launch_bounds__(LNG_THREADS, 2) void gemm_ln_kernel(const GemmLnParams p) {
-  constexpr int BK2 = 32, NS = 3;
-  constexpr int WN = BN / 2, NT = WN / 16, NP = NT / 2, MT = BMT / 32;   // wave tile = BMT/2 rows x BN/2 columns
-  constexpr int STAGE_BYTES = (BMT + BN) * BK2 * 2;
-  constexpr int A_LD = BMT * BK2 * 2 / (4 * 1024);     // 1 KiB DMA pieces per wave per stage
-  constexpr int B_LD = BN * BK2 * 2 / (4 * 1024);
-  constexpr int PER_STAGE = A_LD + B_LD;
+  using Ring = RingShape<BMT, BN>;
+  constexpr int BK2 = Ring::BK2, NS = Ring::NS, STAGE_BYTES = Ring::STAGE_BYTES, WN = Ring::WN, NT = Ring::NT, NP = NT / 2, MT = Ring::MT;
+  constexpr int A_LD = Ring::A_LD, B_LD = Ring::B_LD, PER_STAGE = Ring::PER_STAGE;
   constexpr int TAIL_LOADS = MT * NP + 2 * NP;         // residual rows + bias vectors, per lane
-  static_assert(NT % 2 == 0 && A_LD >= 1 && B_LD >= 1, "tile shape");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -76,12 +69,12 @@ __global__ __launch_bounds__(LNG_THREADS, 2) void gemm_ln_kernel(const GemmLnPar
   for (int i = 0; i < A_LD; ++i) {
     const int row = (wave * A_LD + i) * 16 + prow;
     const int gm = min(m0 + row, p.M - 1);
-    a_src[i] = p.A + (long)gm * p.lda + (pch ^ lswz64(row)) * 8;
+    a_src[i] = p.A + (long)gm * p.lda + (pch ^ ring_swz64(row)) * 8;
   }
 #pragma unroll
   for (int i = 0; i < B_LD; ++i) {
     const int row = (wave * B_LD + i) * 16 + prow;
-    b_src[i] = p.B + (long)row * p.ldb + (pch ^ lswz64(row)) * 8;
+    b_src[i] = p.B + (long)row * p.ldb + (pch ^ ring_swz64(row)) * 8;
   }
   const int nk = p.K / BK2;          // >= 2 (host checks)
   auto issue = [&](int ks) {
@@ -116,8 +109,8 @@ __global__ __launch_bounds__(LNG_THREADS, 2) void gemm_ln_kernel(const GemmLnPar
 
   // the device-resident dropout step: loaded first, so it is the OLDEST entry of the vmcnt queue and never waited for
   const IqRng rng = p.drop_on ? rng_resolve(p.rng) : p.rng;
-  { // de-phase co-resident workgroups (gemm_nt.hip)
-    const int d = (int)(((unsigned)blockIdx.x * 2654435761u) >> 30) * 2;
+  { // de-phase co-resident workgroups
+    const int d = ring_phase() * 2;
     for (int i = 0; i < d; ++i) __builtin_amdgcn_s_sleep(8);
   }
   issue(0);
@@ -130,12 +123,12 @@ __global__ __launch_bounds__(LNG_THREADS, 2) void gemm_ln_kernel(const GemmLnPar
 #pragma unroll
     for (int i = 0; i < MT; ++i) {
       const int row = wm * (BMT / 2) + i * 16 + (lane & 15);
-      af[i] = *reinterpret_cast<const bf16x8*>(As + row * BK2 + (ch ^ lswz64(row)) * 8);
+      af[i] = *reinterpret_cast<const bf16x8*>(As + row * BK2 + (ch ^ ring_swz64(row)) * 8);
     }
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
       const int row = wn * WN + j * 16 + (lane & 15);
-      bfr[j] = *reinterpret_cast<const bf16x8*>(Bs + row * BK2 + (ch ^ lswz64(row)) * 8);
+      bfr[j] = *reinterpret_cast<const bf16x8*>(Bs + row * BK2 + (ch ^ ring_swz64(row)) * 8);
     }
 #pragma unroll
     for (int i = 0; i < MT; ++i)
@@ -148,21 +141,15 @@ __global__ __launch_bounds__(LNG_THREADS, 2) void gemm_ln_kernel(const GemmLnPar
   // The last two stages are peeled: a loop body that also held the tail's register loads made the compiler drain the
   // whole queue (vmcnt(0)) on every iteration.
   for (int ks = 0; ks + 2 < nk; ++ks) {
-    asm volatile("s_waitcnt vmcnt(%0)" :: "n"(PER_STAGE) : "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
+    wait_barrier<PER_STAGE>();
     issue(ks + 2);
     compute(ks);
   }
-  asm volatile("s_waitcnt vmcnt(%0)" :: "n"(PER_STAGE) : "memory");          // stage nk-2 landed, nk-1 in flight
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
+  wait_barrier<PER_STAGE>();                                                  // stage nk-2 landed, nk-1 in flight
   issue_tail();                                                               // every stage is issued: the tail's loads go
   asm volatile("" ::: "memory");                                              // ... now, not after this stage's MFMAs
   compute(nk - 2);
-  asm volatile("s_waitcnt vmcnt(%0)" :: "n"(TAIL_LOADS) : "memory");         // stage nk-1 landed, only the tail's loads fly
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
+  wait_barrier<TAIL_LOADS>();                                                 // stage nk-1 landed, only the tail's loads fly
   compute(nk - 1);
 
   // ---- tail -----------------------------------------------------------------------------------------------------
@@ -274,7 +261,6 @@ __global__ __launch_bounds__(LNG_THREADS, 2) void gemm_ln_kernel(const GemmLnPar
 // LDS: A0 / A1 = the first / second 32 rows of every wave row (128 rows x 128 B, 16 KiB), B0 / B1 = the W rows of column
 // half 0 / 1 (96 x 128 B, 12 KiB; 12 DMA pieces for 8 waves: waves 4..7 request one of theirs twice), two sets: 112 KiB.
 constexpr int LNB_THREADS = 512, LNB_AUNIT = 16384;
-constexpr int lnb_vmcnt(int n) { return (n & 15) | ((n >> 4) << 14) | 0x0F70; }
 
 template <int BN>      // D = 192
 __global__ __launch_bounds__(LNB_THREADS, 1) void gemm_ln_band_kernel(const GemmLnParams p, int nwg) {
@@ -341,7 +327,7 @@ __global__ __launch_bounds__(LNB_THREADS, 1) void gemm_ln_band_kernel(const Gemm
   issue_a(0); issue_b(0); issue_b(1); issue_a(1);
   iset = 1; ikt = 1;
   issue_a(0); issue_b(0);
-  __builtin_amdgcn_s_waitcnt(lnb_vmcnt(6));                        // A0 B0 B1 of K-tile 0 landed
+  __builtin_amdgcn_s_waitcnt(vmcnt_imm(6));                        // A0 B0 B1 of K-tile 0 landed
   __builtin_amdgcn_s_barrier();
   if (half == 1) __builtin_amdgcn_s_barrier();                     // half 1 runs one phase-half behind
 
@@ -371,10 +357,10 @@ __global__ __launch_bounds__(LNB_THREADS, 1) void gemm_ln_band_kernel(const Gemm
     }
   };
   auto wait_left = [&](int left) {
-    if (left == 8) __builtin_amdgcn_s_waitcnt(lnb_vmcnt(8));
-    else if (left == 6) __builtin_amdgcn_s_waitcnt(lnb_vmcnt(6));
-    else if (left == 2) __builtin_amdgcn_s_waitcnt(lnb_vmcnt(2));
-    else if (left == 0) __builtin_amdgcn_s_waitcnt(lnb_vmcnt(0));
+    if (left == 8) __builtin_amdgcn_s_waitcnt(vmcnt_imm(8));
+    else if (left == 6) __builtin_amdgcn_s_waitcnt(vmcnt_imm(6));
+    else if (left == 2) __builtin_amdgcn_s_waitcnt(vmcnt_imm(2));
+    else if (left == 0) __builtin_amdgcn_s_waitcnt(vmcnt_imm(0));
   };
   auto sync_a = [&](int left) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -553,8 +539,8 @@ static int band_workgroups(int M, int D, int K) {
 
 template <int BMT, int BN>
 int launch(const GemmLnParams& p, hipStream_t st) {
-  const size_t lds = (size_t)3 * (BMT + BN) * 32 * 2;
-  static_assert(3 * (BMT + BN) * 32 * 2 >= 4 * BMT * 4, "the reduction scratch fits in the ring");
+  const size_t lds = RingShape<BMT, BN>::BYTES;
+  static_assert(RingShape<BMT, BN>::BYTES >= 4 * BMT * 4, "the reduction scratch fits in the ring");
   auto k = gemm_ln_kernel<BMT, BN>;
   if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   k<<<(p.M + BMT - 1) / BMT, LNG_THREADS, lds, st>>>(p);
@@ -580,13 +566,7 @@ extern "C" int iq_gemm_bf16_ln(const void* A, int lda, const void* W, int ldw, c
   p.lda = lda; p.ldb = ldw; p.M = M; p.K = K;
   p.bias = bias; p.residual = (const bf16*)residual; p.ldr = ldr;
   p.gamma = gamma; p.beta = beta; p.mean = mean; p.rstd = rstd; p.eps = eps;
-  if (drop && drop->p > 0.f) {
-    if (drop->p >= 1.f) return IQ_ERR_ARG;
-    p.drop_on = 1;
-    p.rng.seed = drop->seed; p.rng.step = drop->step; p.rng.site = drop->site; p.rng.step_dev = drop->step_dev;
-    p.thresh = dropout_thresh(drop->p);
-    p.dscale = dropout_scale(drop->p);
-  }
+  if (!dropout_unpack(drop, &p.drop_on, &p.rng, &p.thresh, &p.dscale)) return IQ_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
   IQ_PROF(IQ_FAM_GEMM_NT, st);
   // A + W + residual read, Z + X written (+ bias, gamma, beta, statistics)

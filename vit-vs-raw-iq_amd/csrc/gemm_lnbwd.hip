@@ -12,7 +12,7 @@
 // stored dX (M*D*2 B), and iq_ln_bwd re-read it; here the rounded dX tile crosses LDS instead of HBM: 23 launches and
 // 2*M*D*2 bytes per LayerNorm disappear.  The gamma / beta partial rows join the layer's slab reduce as before.
 //
-// Whole-row tile 128 x D (D = 128 | 192), 4 waves 2 x 2, the RESK main loop of gemm_nt.hip: operands AND the residual
+// Whole-row tile 128 x D (D = 128 | 192), 4 waves 2 x 2, the RESK main loop of gemm_nt.hip (geometry: gemm_ring.h): operands AND the residual
 // arrive through one global_load_lds ring (residual stages are accumulated against identity fragments).
 // Tail: the accumulators are rounded to bf16 (as the unfused GEMM stored them) into a row-major LDS image over the
 // drained ring, and the workgroup then runs ln_bwd_kernel's own row-per-lane-group arithmetic on it (LPR lanes x NV
@@ -24,14 +24,13 @@
 
 #include "common.h"
 #include "gemm_common.h"
+#include "gemm_ring.h"
 #include "iqvit.h"
 #include "prof.h"
 
 namespace {
 
 constexpr int LB_THREADS = 256;
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void gbl_cvoid_t;
 
 struct LnBwdParams {
   const bf16* A; const bf16* B; const bf16* residual;     // [M,K], [D,K], [M,D]
@@ -42,20 +41,14 @@ struct LnBwdParams {
   int drop_on; IqRng rng; uint32_t thresh; float dscale;
 };
 
-__device__ __forceinline__ int bswz64(int row) { return (0x78 >> (((row >> 2) & 3) * 2)) & 3; }   // {0,2,3,1}: gemm_nt.hip
-
 template <int BMT, int BN>
 __global__ __launch_bounds__(LB_THREADS, 2) void gemm_lnbwd_kernel(const LnBwdParams p) {
-  constexpr int BK2 = 32, NS = 3;
-  constexpr int WN = BN / 2, NT = WN / 16, NP = NT / 2, MT = BMT / 32;
-  constexpr int STAGE_BYTES = (BMT + BN) * BK2 * 2;
-  constexpr int A_LD = BMT * BK2 * 2 / (4 * 1024);
-  constexpr int B_LD = BN * BK2 * 2 / (4 * 1024);
-  constexpr int PER_STAGE = A_LD + B_LD;
-  constexpr int NRS = BN / BK2;                      // residual stages
+  using Ring = RingShape<BMT, BN>;
+  constexpr int BK2 = Ring::BK2, NS = Ring::NS, STAGE_BYTES = Ring::STAGE_BYTES, WN = Ring::WN, NT = Ring::NT, NP = NT / 2, MT = Ring::MT;
+  constexpr int A_LD = Ring::A_LD, B_LD = Ring::B_LD, PER_STAGE = Ring::PER_STAGE, NRS = Ring::NRS;
   constexpr int TAIL_LOADS = (BMT / (4 * (64 / ((BN == 192) ? 8 : 16)))) * (BN / (8 * ((BN == 192) ? 8 : 16)));   // ITER * NV Z vectors
   constexpr int N = BN;
-  static_assert(NT % 2 == 0 && NRS >= 2, "tile shape");
+  static_assert(NRS >= 2, "tile shape");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -78,13 +71,13 @@ __global__ __launch_bounds__(LB_THREADS, 2) void gemm_lnbwd_kernel(const LnBwdPa
   for (int i = 0; i < A_LD; ++i) {
     const int row = (wave * A_LD + i) * 16 + prow;
     const int gm = min(m0 + row, p.M - 1);
-    a_src[i] = p.A + (long)gm * p.lda + (pch ^ bswz64(row)) * 8;
-    r_src[i] = p.residual + (long)gm * p.ldr + (pch ^ bswz64(row)) * 8;
+    a_src[i] = p.A + (long)gm * p.lda + (pch ^ ring_swz64(row)) * 8;
+    r_src[i] = p.residual + (long)gm * p.ldr + (pch ^ ring_swz64(row)) * 8;
   }
 #pragma unroll
   for (int i = 0; i < B_LD; ++i) {
     const int row = (wave * B_LD + i) * 16 + prow;
-    b_src[i] = p.B + (long)row * p.ldb + (pch ^ bswz64(row)) * 8;
+    b_src[i] = p.B + (long)row * p.ldb + (pch ^ ring_swz64(row)) * 8;
   }
   const int nk = p.K / BK2;               // >= 2
   // identity fragments (the weight-side MFMA operand of a residual stage): gemm_nt.hip
@@ -140,7 +133,7 @@ __global__ __launch_bounds__(LB_THREADS, 2) void gemm_lnbwd_kernel(const LnBwdPa
   f32x4 side_g = {0.f, 0.f, 0.f, 0.f};
   if (tid < N / 4) side_g = *reinterpret_cast<const f32x4*>(p.gamma + tid * 4);
   {
-    const int d = (int)(((unsigned)blockIdx.x * 2654435761u) >> 30) * 2;
+    const int d = ring_phase() * 2;
     for (int i = 0; i < d; ++i) __builtin_amdgcn_s_sleep(8);
   }
   issue(0);
@@ -150,10 +143,9 @@ __global__ __launch_bounds__(LB_THREADS, 2) void gemm_lnbwd_kernel(const LnBwdPa
   const int ch = lane >> 4;
   // main stages: stage ks landed (stage ks+1 stays in flight), barrier, refill the vacated slot
   for (int ks = 0; ks < nk; ++ks) {
-    if (ks + 1 < nk) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(PER_STAGE) : "memory");
-    else asm volatile("s_waitcnt vmcnt(%0)" :: "n"(A_LD) : "memory");            // the next stage is a residual stage
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
+    if (ks + 1 < nk) wait_vmcnt<PER_STAGE>();
+    else wait_vmcnt<A_LD>();                                                      // the next stage is a residual stage
+    ring_barrier();
     issue(ks + 2);                                                                // ks + 2 < ntot always (NRS >= 2)
     const bf16* As = reinterpret_cast<const bf16*>(smem + (ks % NS) * STAGE_BYTES);
     const bf16* Bs = As + BMT * BK2;
@@ -161,12 +153,12 @@ __global__ __launch_bounds__(LB_THREADS, 2) void gemm_lnbwd_kernel(const LnBwdPa
 #pragma unroll
     for (int i = 0; i < MT; ++i) {
       const int row = wm * (BMT / 2) + i * 16 + (lane & 15);
-      af[i] = *reinterpret_cast<const bf16x8*>(As + row * BK2 + (ch ^ bswz64(row)) * 8);
+      af[i] = *reinterpret_cast<const bf16x8*>(As + row * BK2 + (ch ^ ring_swz64(row)) * 8);
     }
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
       const int row = wn * WN + j * 16 + (lane & 15);
-      bfr[j] = *reinterpret_cast<const bf16x8*>(Bs + row * BK2 + (ch ^ bswz64(row)) * 8);
+      bfr[j] = *reinterpret_cast<const bf16x8*>(Bs + row * BK2 + (ch ^ ring_swz64(row)) * 8);
     }
 #pragma unroll
     for (int i = 0; i < MT; ++i)
@@ -183,7 +175,7 @@ __global__ __launch_bounds__(LB_THREADS, 2) void gemm_lnbwd_kernel(const LnBwdPa
 #pragma unroll
       for (int i = 0; i < MT; ++i) {
         const int row = wm * (BMT / 2) + i * 16 + (lane & 15);
-        af[i] = *reinterpret_cast<const bf16x8*>(As + row * BK2 + (ch ^ bswz64(row)) * 8);
+        af[i] = *reinterpret_cast<const bf16x8*>(As + row * BK2 + (ch ^ ring_swz64(row)) * 8);
       }
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
@@ -194,31 +186,21 @@ __global__ __launch_bounds__(LB_THREADS, 2) void gemm_lnbwd_kernel(const LnBwdPa
       }
     }
   };
-  auto unrolled = [&](auto self, auto tc) -> void {
+  static_for<NRS>([&](auto tc) {
     constexpr int t = decltype(tc)::value;
-    if constexpr (t < NRS) {
-      // stage nk + t landed?  younger entries of the queue: the next residual stage, or the tail's loads, or nothing
-      if constexpr (t + 2 < NRS) {               // a later stage will still be issued here
-        asm volatile("s_waitcnt vmcnt(%0)" :: "n"(A_LD) : "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        issue(nk + t + 2);
-      } else if constexpr (t + 2 == NRS) {       // every stage is issued: the tail's loads go behind the last one
-        asm volatile("s_waitcnt vmcnt(%0)" :: "n"(A_LD) : "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        issue_tail();
-        asm volatile("" ::: "memory");
-      } else {                                   // last stage: only the tail's loads stay in flight
-        asm volatile("s_waitcnt vmcnt(%0)" :: "n"(TAIL_LOADS) : "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-      }
-      residual_stage(tc);
-      self(self, std::integral_constant<int, t + 1>{});
+    // stage nk + t landed?  younger entries of the queue: the next residual stage, or the tail's loads, or nothing
+    if constexpr (t + 2 < NRS) {               // a later stage will still be issued here
+      wait_barrier<A_LD>();
+      issue(nk + t + 2);
+    } else if constexpr (t + 2 == NRS) {       // every stage is issued: the tail's loads go behind the last one
+      wait_barrier<A_LD>();
+      issue_tail();
+      asm volatile("" ::: "memory");
+    } else {                                   // last stage: only the tail's loads stay in flight
+      wait_barrier<TAIL_LOADS>();
     }
-  };
-  unrolled(unrolled, std::integral_constant<int, 0>{});
+    residual_stage(tc);
+  });
 
   // ---- tail ------------------------------------------------------------------------------------------------------------
   // (1) dX, rounded to bf16 as the unfused GEMM stored it, into a row-major image over the drained ring
@@ -329,7 +311,7 @@ __global__ __launch_bounds__(LB_THREADS, 2) void gemm_lnbwd_kernel(const LnBwdPa
 
 template <int BMT, int BN>
 int launch(const LnBwdParams& p, hipStream_t st) {
-  const size_t lds = (size_t)3 * (BMT + BN) * 32 * 2 + (2 * BMT + BN) * sizeof(float);   // ring + mean | rstd | gamma
+  const size_t lds = RingShape<BMT, BN>::BYTES + (2 * BMT + BN) * sizeof(float);   // ring + mean | rstd | gamma
   auto k = gemm_lnbwd_kernel<BMT, BN>;
   if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   k<<<(p.M + BMT - 1) / BMT, LB_THREADS, lds, st>>>(p);
@@ -368,13 +350,7 @@ extern "C" int iq_gemm_bf16_lnbwd(const void* A, int lda, const void* Wt, int ld
   p.lda = lda; p.ldb = ldw; p.ldr = ldr; p.M = M; p.K = K;
   p.Z = (const bf16*)z; p.mean = mean; p.rstd = rstd; p.gamma = gamma;
   p.dZ = (bf16*)dz; p.dY = (bf16*)dy; p.partial = partial;
-  if (drop && drop->p > 0.f) {
-    if (drop->p >= 1.f || !dy) return IQ_ERR_ARG;
-    p.drop_on = 1;
-    p.rng.seed = drop->seed; p.rng.step = drop->step; p.rng.site = drop->site; p.rng.step_dev = drop->step_dev;
-    p.thresh = dropout_thresh(drop->p);
-    p.dscale = dropout_scale(drop->p);
-  }
+  if (!dropout_unpack(drop, &p.drop_on, &p.rng, &p.thresh, &p.dscale) || (p.drop_on && !dy)) return IQ_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
   IQ_PROF(IQ_FAM_GEMM_NT, st);
   // A + Wt + residual + Z read, dZ (+ dY) written

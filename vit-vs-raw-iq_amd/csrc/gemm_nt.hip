@@ -20,6 +20,7 @@
 
 #include "common.h"
 #include "gemm_common.h"
+#include "gemm_ring.h"
 #include "iqvit.h"
 #include "prof.h"
 
@@ -128,15 +129,9 @@ __global__ __launch_bounds__(GEMM_THREADS) void gemm_nt_kernel(const GemmParams 
 // s_waitcnt vmcnt + raw s_barrier (guide 5, "Pipelining across barriers").  The register-staged
 // kernel above keeps one stage in flight and exposes the full HBM latency on every K step
 // (measured 2.0-2.9 TB/s algorithmic on the ViT-Tiny shapes); this one is bounded by bytes.
-// Stage = [128 + BN rows][64 B]; 16 B chunk c of row r sits at chunk c ^ f(r>>2), f = {0,2,3,1} (chosen so
-// that the 16-lane groups of ds_read_b128, which mix lanes of chunk c and c+1, hit 16 distinct slots): the DMA
-// writes LDS lane-linearly, so the swizzle is applied to the per-lane SOURCE address (guide rule 21)
-// and again on the ds_read_b128 fragment reads, which are then bank-conflict free.
+// Stage layout, swizzle (ring_swz64) and the stage-head waits: gemm_ring.h, shared with gemm_ln.hip and gemm_lnbwd.hip.
 // Rows past M / N are clamped to the last valid row (their products are never stored).
-__device__ __forceinline__ int swz64(int row) { return (0x78 >> (((row >> 2) & 3) * 2)) & 3; }
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void gbl_cvoid_t;
-
+//
 // RESK ("residual as K"): for C = A W^T + R with no bias / activation / dropout (the data-gradient GEMMs) and a tile that
 // spans the whole row (BN == N), R is streamed through the SAME ring as BN/32 extra K stages and accumulated by MFMAs
 // against identity fragments built in registers: acc += R * I.  Exact (x * 1.0 and the same final fp32 add as the
@@ -149,13 +144,9 @@ template <int BMT, int BN, int EPI, bool RESK = false>
 // Bias-only variants keep the plain loop and the default allocation (99 VGPR + 64 AGPR, three workgroups per CU): for
 // them the early form measured SLOWER (FFN1 shape 33.2 -> 38.5 us, QKV 27.7 -> 31.5), with nothing worth prefetching.
 __global__ __launch_bounds__(GEMM_THREADS, RESK ? 3 : ((EPI & ~EPI_PE) == 0 ? 1 : 2)) void gemm_nt_async_kernel(const GemmParams p) {
-  constexpr int BK2 = 32;
-  constexpr int WN = BN / 2, NT = WN / 16, MT = BMT / 32;   // wave tile = BMT/2 rows x BN/2 cols
-  constexpr int STAGE_BYTES = (BMT + BN) * BK2 * 2;
-  constexpr int NS = 3;
-  constexpr int A_LD = BMT * BK2 * 2 / (4 * 1024);     // 1 KiB DMA pieces per wave per stage: A 2 | 1
-  constexpr int B_LD = BN * BK2 * 2 / (4 * 1024);      //                                      B 2 | 1
-  constexpr int PER_STAGE = A_LD + B_LD;
+  using Ring = RingShape<BMT, BN>;
+  constexpr int BK2 = Ring::BK2, NS = Ring::NS, STAGE_BYTES = Ring::STAGE_BYTES, WN = Ring::WN, NT = Ring::NT, MT = Ring::MT;
+  constexpr int A_LD = Ring::A_LD, B_LD = Ring::B_LD, PER_STAGE = Ring::PER_STAGE;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -178,16 +169,16 @@ __global__ __launch_bounds__(GEMM_THREADS, RESK ? 3 : ((EPI & ~EPI_PE) == 0 ? 1 
   for (int i = 0; i < A_LD; ++i) {
     const int row = (wave * A_LD + i) * 16 + prow;
     const int gm = min(m0 + row, p.M - 1);
-    a_src[i] = p.A + (long)gm * p.lda + (pch ^ swz64(row)) * 8;
+    a_src[i] = p.A + (long)gm * p.lda + (pch ^ ring_swz64(row)) * 8;
   }
 #pragma unroll
   for (int i = 0; i < B_LD; ++i) {
     const int row = (wave * B_LD + i) * 16 + prow;
     const int gn = min(n0 + row, p.N - 1);
-    b_src[i] = p.B + (long)gn * p.ldb + (pch ^ swz64(row)) * 8;
+    b_src[i] = p.B + (long)gn * p.ldb + (pch ^ ring_swz64(row)) * 8;
   }
   const int nk = p.K / BK2;
-  const int ntot = nk + (RESK ? BN / BK2 : 0);
+  const int ntot = nk + (RESK ? Ring::NRS : 0);
   const bf16* r_src[A_LD];
   bf16x8 idf[2];
   if (RESK) {
@@ -195,7 +186,7 @@ __global__ __launch_bounds__(GEMM_THREADS, RESK ? 3 : ((EPI & ~EPI_PE) == 0 ? 1 
     for (int i = 0; i < A_LD; ++i) {
       const int row = (wave * A_LD + i) * 16 + prow;
       const int gm = min(m0 + row, p.M - 1);
-      r_src[i] = p.residual + (long)gm * p.ldr + (pch ^ swz64(row)) * 8;
+      r_src[i] = p.residual + (long)gm * p.ldr + (pch ^ ring_swz64(row)) * 8;
     }
     // identity fragments (the weight-side MFMA operand): lane (n = lane & 15, k = 8 (lane >> 4) + e) of the 16-column
     // tile h of a 32-wide residual stage holds 1 where 16 h + n == k
@@ -229,9 +220,7 @@ __global__ __launch_bounds__(GEMM_THREADS, RESK ? 3 : ((EPI & ~EPI_PE) == 0 ? 1 
 #define IQ_STAMP(i) do {} while (0)
 #endif
   if (p.stagger > 0) {
-    // Co-resident workgroups otherwise run their phases in lockstep (all waiting on HBM, then all on the MFMA
-    // pipe, then all storing): de-phase them once at launch; the offset persists as slots are refilled.
-    const int d = (int)(((unsigned)blockIdx.x * 2654435761u) >> 30) * p.stagger;   // 0..3 x stagger
+    const int d = ring_phase() * p.stagger;
     for (int i = 0; i < d; ++i) __builtin_amdgcn_s_sleep(8);
   }
   // the tail's registers; the device-resident dropout step is loaded FIRST (oldest entry of the in-order vmcnt queue)
@@ -245,13 +234,12 @@ __global__ __launch_bounds__(GEMM_THREADS, RESK ? 3 : ((EPI & ~EPI_PE) == 0 ? 1 
   // have (barrier, which also says stage ks-1 is no longer read), the slot ks-1 vacated is refilled
   auto stage_begin = [&](int ks) {
     if (ks + 1 < ntot) {
-      if (!RESK || ks + 1 < nk) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(PER_STAGE) : "memory");
-      else asm volatile("s_waitcnt vmcnt(%0)" :: "n"(A_LD) : "memory");
+      if (!RESK || ks + 1 < nk) wait_vmcnt<PER_STAGE>();
+      else wait_vmcnt<A_LD>();                            // the next stage is a residual stage
     } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      wait_vmcnt<0>();
     }
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
+    ring_barrier();
     if (ks + 2 < ntot) issue(ks + 2);
   };
   const int ch = lane >> 4;
@@ -262,12 +250,12 @@ __global__ __launch_bounds__(GEMM_THREADS, RESK ? 3 : ((EPI & ~EPI_PE) == 0 ? 1 
 #pragma unroll
     for (int i = 0; i < MT; ++i) {
       const int row = wm * (BMT / 2) + i * 16 + (lane & 15);
-      af[i] = *reinterpret_cast<const bf16x8*>(As + row * BK2 + (ch ^ swz64(row)) * 8);
+      af[i] = *reinterpret_cast<const bf16x8*>(As + row * BK2 + (ch ^ ring_swz64(row)) * 8);
     }
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
       const int row = wn * WN + j * 16 + (lane & 15);
-      bfr[j] = *reinterpret_cast<const bf16x8*>(Bs + row * BK2 + (ch ^ swz64(row)) * 8);
+      bfr[j] = *reinterpret_cast<const bf16x8*>(Bs + row * BK2 + (ch ^ ring_swz64(row)) * 8);
     }
 #ifdef IQ_NT_NO_MFMA   // ablation build (scripts/dbg/ablate.py): timing only
 #pragma unroll
@@ -298,20 +286,14 @@ __global__ __launch_bounds__(GEMM_THREADS, RESK ? 3 : ((EPI & ~EPI_PE) == 0 ? 1 
       compute(ks);
     }
     if (nk >= 2) {
-      asm volatile("s_waitcnt vmcnt(%0)" :: "n"(PER_STAGE) : "memory");      // stage nk-2 landed, nk-1 in flight
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
+      wait_barrier<PER_STAGE>();                                              // stage nk-2 landed, nk-1 in flight
       epi_load_early<MT, NT, EPIX>(p, R, row0, col0, lane);
       asm volatile("" ::: "memory");                                          // ... issued now, not after this stage's MFMAs
       compute(nk - 2);
-      asm volatile("s_waitcnt vmcnt(%0)" :: "n"(EARLY) : "memory");          // stage nk-1 landed; only the tail's loads fly
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
+      wait_barrier<EARLY>();                                                  // stage nk-1 landed; only the tail's loads fly
       compute(nk - 1);
     } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
+      wait_barrier<0>();
       epi_load_early<MT, NT, EPIX>(p, R, row0, col0, lane);
       asm volatile("" ::: "memory");
       compute(0);
@@ -327,7 +309,7 @@ __global__ __launch_bounds__(GEMM_THREADS, RESK ? 3 : ((EPI & ~EPI_PE) == 0 ? 1 
     // residual stage t covers columns [32 t, 32 t + 32) = column tiles 2t and 2t+1 of the row: the wave that owns them
     // (wn == 2t / NT) accumulates R * I into exactly those two tiles.  Fully unrolled: every accumulator index is static
     // (one loop with a run-time tile index made the compiler shuttle all accumulators through copies every K step).
-    constexpr int NRS = BN / BK2;
+    constexpr int NRS = Ring::NRS;
 #pragma unroll
     for (int t = 0; t < NRS; ++t) {
       stage_begin(nk + t);
@@ -337,7 +319,7 @@ __global__ __launch_bounds__(GEMM_THREADS, RESK ? 3 : ((EPI & ~EPI_PE) == 0 ? 1 
 #pragma unroll
         for (int i = 0; i < MT; ++i) {
           const int row = wm * (BMT / 2) + i * 16 + (lane & 15);
-          af[i] = *reinterpret_cast<const bf16x8*>(As + row * BK2 + (ch ^ swz64(row)) * 8);
+          af[i] = *reinterpret_cast<const bf16x8*>(As + row * BK2 + (ch ^ ring_swz64(row)) * 8);
         }
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
@@ -397,14 +379,7 @@ extern "C" int iq_gemm_bf16_nt(const void* A, int lda, const void* B, int ldb, v
     p.bias = epi->bias; p.relu = epi->relu;
     p.pe = epi->pe; p.tok = epi->tok; p.seq = epi->seq; p.cls_off = epi->cls_off;
     if (epi->tok < 0 || (epi->tok > 0 && epi->seq < epi->tok + epi->cls_off)) return IQ_ERR_ARG;
-    if (epi->drop.p > 0.f) {
-      if (epi->drop.p >= 1.f) return IQ_ERR_ARG;
-      p.drop_on = 1;
-      p.rng.seed = epi->drop.seed; p.rng.step = epi->drop.step; p.rng.site = epi->drop.site;
-      p.rng.step_dev = epi->drop.step_dev;
-      p.thresh = dropout_thresh(epi->drop.p);
-      p.dscale = dropout_scale(epi->drop.p);
-    }
+    if (!dropout_unpack(&epi->drop, &p.drop_on, &p.rng, &p.thresh, &p.dscale)) return IQ_ERR_ARG;
     p.gate = (const bf16*)epi->gate; p.ldg = epi->ldg; p.gate_scale = epi->gate_scale;
     p.residual = (const bf16*)epi->residual; p.ldr = epi->ldr;
     if ((p.gate && (p.ldg % 8)) || (p.residual && (p.ldr % 8))) return IQ_ERR_UNSUPPORTED;

@@ -32,11 +32,8 @@
 namespace {
 
 constexpr int WB_THREADS = 512, WB_TN = 256, WB_MT = 64, WB_AUNIT = 16384, WB_MAXP = 4;
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void gbl_cvoid_t;
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
-constexpr int wb_vmcnt(int n) { return (n & 15) | ((n >> 4) << 14) | 0x0F70; }
 
 struct WbProb {
   const bf16* A; const bf16* B;      // A: its columns are the output rows n', B: the output columns k'
@@ -144,7 +141,7 @@ __global__ __launch_bounds__(WB_THREADS, 1) void wgrad_big_kernel(const WbGroup 
   issue_a(0); issue_b(0); issue_b(1); issue_a(1);
   issue_advance();
   if (total > 1) { issue_a(0); issue_b(0); }
-  if (total > 1) __builtin_amdgcn_s_waitcnt(wb_vmcnt(L_Y)); else __builtin_amdgcn_s_waitcnt(wb_vmcnt(2));
+  if (total > 1) __builtin_amdgcn_s_waitcnt(vmcnt_imm(L_Y)); else __builtin_amdgcn_s_waitcnt(vmcnt_imm(2));
   __builtin_amdgcn_s_barrier();                       // barrier 0: A0 B0 B1 of step 0 visible
   if (wr == 1) __builtin_amdgcn_s_barrier();          // half 1 runs one phase-half behind
 
@@ -178,10 +175,10 @@ __global__ __launch_bounds__(WB_THREADS, 1) void wgrad_big_kernel(const WbGroup 
     }
   };
   auto wait_left = [&](int left) {
-    if (left == L_X) __builtin_amdgcn_s_waitcnt(wb_vmcnt(L_X));
-    else if (left == L_Y) __builtin_amdgcn_s_waitcnt(wb_vmcnt(L_Y));
-    else if (left == 2) __builtin_amdgcn_s_waitcnt(wb_vmcnt(2));
-    else if (left == 0) __builtin_amdgcn_s_waitcnt(wb_vmcnt(0));
+    if (left == L_X) __builtin_amdgcn_s_waitcnt(vmcnt_imm(L_X));
+    else if (left == L_Y) __builtin_amdgcn_s_waitcnt(vmcnt_imm(L_Y));
+    else if (left == 2) __builtin_amdgcn_s_waitcnt(vmcnt_imm(2));
+    else if (left == 0) __builtin_amdgcn_s_waitcnt(vmcnt_imm(0));
   };
   auto sync_a = [&](int left) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");

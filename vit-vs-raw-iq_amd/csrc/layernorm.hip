@@ -289,16 +289,9 @@ extern "C" int iq_ln_bwd(const void* dx, const void* z, const float* mean, const
   if ((dgamma == nullptr) != (dbeta == nullptr)) return IQ_ERR_ARG;
   const bool reduce_now = dgamma != nullptr;   // else: partial rows stay in ws for a fused reduction (iq_reduce_seg_t)
   if (!ln_shape(D, &s)) return IQ_ERR_UNSUPPORTED;
-  const bool dropping = drop && drop->p > 0.f;
+  int dropping; IqRng rng; uint32_t thresh; float dscale;
+  (void)dropout_unpack(drop, &dropping, &rng, &thresh, &dscale);      // (p >= 1 is not refused here)
   if (dropping && !dy) return IQ_ERR_ARG;
-  IqRng rng = {0, 0, 0, nullptr};
-  uint32_t thresh = 0;
-  float dscale = 1.f;
-  if (dropping) {
-    rng.seed = drop->seed; rng.step = drop->step; rng.site = drop->site; rng.step_dev = drop->step_dev;
-    thresh = dropout_thresh(drop->p);
-    dscale = dropout_scale(drop->p);
-  }
   hipStream_t st = (hipStream_t)stream;
   IQ_PROF(IQ_FAM_LN_BWD, st);
   IQ_PROF_K(2.0 * (double)M * D * (3 + (dropping ? 1 : 0)) + 8.0 * M, 0.0, "ln_bwd_kernel(D=%d)", D);

@@ -574,14 +574,6 @@ inline int grid_for(size_t n, int per_block, int cap) {
   return (int)b;
 }
 
-inline void fill_rng(const iq_dropout_t* d, int* on, IqRng* r, uint32_t* th, float* sc) {
-  *on = 0; r->seed = 0; r->step = 0; r->site = 0; r->step_dev = nullptr; *th = 0; *sc = 1.f;
-  if (d && d->p > 0.f) {
-    *on = 1; r->seed = d->seed; r->step = d->step; r->site = d->site; r->step_dev = d->step_dev;
-    *th = dropout_thresh(d->p); *sc = dropout_scale(d->p);
-  }
-}
-
 }  // namespace
 
 extern "C" int iq_patchify(const float* src, void* patches, int kind, int B, int C, int H, int W, int p, int Kpad,
@@ -611,7 +603,7 @@ extern "C" int iq_cls_rows(const float* cls, const float* pe, void* x0, int B, i
   if (B <= 0) return IQ_OK;
   if (!cls || !pe || !x0 || (D % 8)) return IQ_ERR_ARG;
   int on; IqRng r; uint32_t th; float sc;
-  fill_rng(drop, &on, &r, &th, &sc);
+  (void)dropout_unpack(drop, &on, &r, &th, &sc);      // (p >= 1 is not refused here)
   const int n = B * (D / 8);
   cls_rows_kernel<<<(n + 255) / 256, 256, 0, (hipStream_t)stream>>>(cls, pe, (bf16*)x0, B, S, D, on, r, th, sc);
   return iq_launch_status();
@@ -623,7 +615,7 @@ extern "C" int iq_embed_bwd_gather(const void* dx0, void* demb, float* dcls, int
   if (B <= 0) return IQ_OK;
   if (!dx0 || !demb || (D % 8) || (has_cls && !dcls)) return IQ_ERR_ARG;
   int on; IqRng r; uint32_t th; float sc;
-  fill_rng(drop, &on, &r, &th, &sc);
+  (void)dropout_unpack(drop, &on, &r, &th, &sc);      // (p >= 1 is not refused here)
   const size_t n = (size_t)B * tok * (D / 8);
   hipStream_t st = (hipStream_t)stream;
   embed_bwd_gather_kernel<<<grid_for(n, 256, 4096), 256, 0, st>>>((const bf16*)dx0, (bf16*)demb, B, S, tok, D,
@@ -765,7 +757,7 @@ int embed_bwd_gather_launch(const void* dx0, void* demb, int B, int S, int tok, 
   IQ_PROF(IQ_FAM_MISC, st);
   if (B <= 0) return IQ_OK;
   int on; IqRng r; uint32_t th; float sc;
-  fill_rng(drop, &on, &r, &th, &sc);
+  (void)dropout_unpack(drop, &on, &r, &th, &sc);      // (p >= 1 is not refused here)
   const size_t n = (size_t)B * tok * (D / 8);
   embed_bwd_gather_kernel<<<grid_for(n, 256, 4096), 256, 0, st>>>((const bf16*)dx0, (bf16*)demb, B, S, tok, D, has_cls ? 1 : 0,
                                                                   on, r, th, sc);
