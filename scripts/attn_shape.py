@@ -20,4 +20,4 @@ lse = torch.empty(B, H, S, device=d); dout = torch.randn(B * S, D, device=d).bfl
 tf = timeit(lambda: L.iq_attn_fwd(qkv.data_ptr(), out.data_ptr(), lse.data_ptr(), B, S, H, dh, st()))
 tb = timeit(lambda: L.iq_attn_bwd(qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(), dqkv.data_ptr(), B, S, H, dh, st()))
 bf, bb = 2 * B * S * 4 * D, 2 * B * S * 8 * D
-print(f"S={S} H={H} dh={dh} B={B} frame={os.environ.get('IQ_TUNE_ATTN_FRAME', 'auto')}: fwd {tf:6.1f} us ({bf / tf / 1e6:6.2f} TB/s)   bwd {tb:6.1f} us ({bb / tb / 1e6:6.2f} TB/s)")
+print(f"S={S} H={H} dh={dh} B={B}: fwd {tf:6.1f} us ({bf / tf / 1e6:6.2f} TB/s)   bwd {tb:6.1f} us ({bb / tb / 1e6:6.2f} TB/s)")

@@ -6,11 +6,12 @@ kernel that ran is read back from the profiling records (iq_prof_kernels).
 Accuracy bound: the project's attention-backward bound (test_gpu_kernels.py::test_attention_fwd_bwd),
 max |err| <= 0.02 * max |grad| + 1e-6 against fp64 autograd of the same attention on the bf16-rounded inputs.
 """
-import ctypes as C
 import math
 
 import pytest
 import torch
+
+from prof_names import kernels_of
 
 pytestmark = pytest.mark.gpu
 
@@ -56,23 +57,10 @@ def once_claims(S, H, dh):
     return dh == 64 and (S + 31) // 32 * 32 <= 224 and not frame_claims(S, H, dh)
 
 
-def kernels_of(L, fn):
-    """Names of the kernels the launch sites recorded while fn() ran."""
-    ms = (C.c_double * 8)()
-    cnt = (C.c_longlong * 8)()
-    torch.cuda.synchronize()
-    L.iq_prof_enable(1)
-    L.iq_prof_collect(ms, cnt)
-    L.iq_prof_kernels(None, 0, 1)
-    try:
-        fn()
-        L.iq_prof_collect(ms, cnt)
-    finally:
-        L.iq_prof_enable(0)
-    need = L.iq_prof_kernels(None, 0, 0)
-    buf = C.create_string_buffer(need + 1)
-    L.iq_prof_kernels(buf, need + 1, 1)
-    return [line.split("\t")[0] for line in buf.value.decode().splitlines()]
+def frame_fwd_claims(S, H, dh):
+    """use_frame(S, frame_fwd_lds(S, H, dh)), restated: the forward's frame holds q, k, v only."""
+    spad = (S + 31) // 32 * 32
+    return S <= 128 and spad * (3 * H * dh + 16) * 2 <= 112 * 1024
 
 
 def forward(L, qkv, Bf, S, H, dh):
@@ -112,25 +100,37 @@ def check_against_fp64(qkv, dout, dqkv, Bf, S, H, dh, what):
 
 # S: the edges of the 16-key unit (16, 17, 208, 209), of the 32-row block (193, 224) and of the S = 197 image (207, 208)
 SMALL = [(S, H, 64, 2) for S in (1, 16, 17, 193, 197, 207, 208, 209, 224) for H in (1, 3, 12)]
+# The edges of the kernel choice, with the (forward, backward) kernel each side must run: S = 128 | 129 (the per-frame kernels
+# end at 128 rows); S = 128 with H = 2 (the forward's frame is 102,400 B of LDS, the backward's 141,312 B > 112 KiB); S = 225
+# (padded length 256 > 224: the two-phase kernel).
+EDGES = {(128, 1, 64, 2): ("attn_frame_fwd_kernel<64>", "attn_frame_bwd_kernel<64>"),
+         (129, 1, 64, 2): ("attn_fwd_kernel<64, false>", "attn_bwd_once_kernel<1024>"),
+         (128, 2, 64, 2): ("attn_frame_fwd_kernel<64>", "attn_bwd_once_kernel<1024>"),
+         (225, 1, 64, 2): ("attn_fwd_kernel<64, false>", "attn_bwd_kernel<64, false>")}
 
 
-@pytest.mark.parametrize("S,H,dh,Bf", [(197, 3, 64, 256)] + SMALL)
+@pytest.mark.parametrize("S,H,dh,Bf", [(197, 3, 64, 256)] + SMALL + list(EDGES))
 def test_bwd_once_matches_fp64_autograd(L, S, H, dh, Bf):
     D = H * dh
     g = torch.Generator(device="cuda").manual_seed(S * 131 + H)
     qkv = torch.randn(Bf * S, 3 * D, device=dev(), generator=g).to(torch.bfloat16)
     dout = torch.randn(Bf * S, D, device=dev(), generator=g).to(torch.bfloat16)
-    out, lse = forward(L, qkv, Bf, S, H, dh)
     res = {}
+    fwd = kernels_of(L, lambda: res.setdefault("fwd", forward(L, qkv, Bf, S, H, dh)))
+    out, lse = res["fwd"]
+    assert fwd == ["attn_frame_fwd_kernel<64>" if frame_fwd_claims(S, H, dh) else "attn_fwd_kernel<64, false>"], fwd
     names = kernels_of(L, lambda: res.setdefault("dqkv", backward(L, qkv, out, dout, lse, Bf, S, H, dh)))
     bwd = [n for n in names if "bwd" in n]
-    if S >= 193:
+    if 193 <= S <= 224:
         assert once_claims(S, H, dh)          # the long shapes must reach the new kernel
     if once_claims(S, H, dh):
         assert len(bwd) == 1 and bwd[0].startswith("attn_bwd_once_kernel<"), names
-    else:
-        assert frame_claims(S, H, dh)
+    elif frame_claims(S, H, dh):
         assert len(bwd) == 1 and bwd[0].startswith("attn_frame_bwd_kernel<"), names
+    else:
+        assert len(bwd) == 1 and bwd[0].startswith("attn_bwd_kernel<"), names
+    if (S, H, dh, Bf) in EDGES:
+        assert (fwd[0], bwd[0]) == EDGES[(S, H, dh, Bf)], (fwd, names)
     check_against_fp64(qkv, dout, res["dqkv"], Bf, S, H, dh, f"S={S} H={H} frames={Bf} ({bwd[0]})")
 
 

@@ -109,6 +109,8 @@ def test_host_only_queries_work_without_a_gpu():
         units = (M + rw - 1) // rw
         assert L.iq_ffn_chain_bwd_partial_rows(M) == (units + nw - 1) // nw, M
         assert L.iq_ffn_chain_gate_bytes(M, 768) == units * 12 * 256, M
+    # the fused data-gradient GEMM + LayerNorm backward: 64-row blocks up to 320 blocks of 128 rows, 128-row blocks above
+    assert L.iq_gemm_lnbwd_partial_rows(40960) == 640 and L.iq_gemm_lnbwd_partial_rows(40961) == 321
 
 
 @pytest.mark.parametrize("name", golden_names())

@@ -27,7 +27,6 @@
 // once, in phase A, and hands dS to phase B's dQ product through an LDS image (5 MFMA products, 16 waves, one workgroup
 // per CU); attn_bwd_kernel (every other shape: masked, chunked, dh 16 / 32) recomputes them in phase B (7 products);
 // attn_frame_bwd_kernel takes short sequences one frame per workgroup.
-#include <stdlib.h>
 
 #include "common.h"
 #include "iqvit.h"
@@ -80,25 +79,13 @@ __device__ __forceinline__ bf16x8 row_frag_gmem(const bf16* base, long ldg, int 
   return v;
 }
 
-// stage rows [r_begin, r_begin+nrows_pad) of a [S, dh] head slice (global row stride ldg) into an LDS image,
-// zero-filling rows >= S
-template <int DH>
-__device__ __forceinline__ void stage_rows(bf16* img, const bf16* base, long ldg, int r_begin, int nrows_pad, int S,
-                                           int tid) {
-  constexpr int CPR = AttCfg<DH>::CPR, LD = AttCfg<DH>::LD;
-  for (int id = tid; id < nrows_pad * CPR; id += ATT_THREADS) {
-    const int r = id / CPR, c = id % CPR;
-    bf16x8 v = {};
-    if (r_begin + r < S) v = *reinterpret_cast<const bf16x8*>(base + (long)(r_begin + r) * ldg + c * 8);
-    *reinterpret_cast<bf16x8*>(img + r * LD + c * 8) = v;
-  }
-}
-
-// Two images at once, loads batched: every thread first REQUESTS UN 16-byte chunks of each image (2 UN loads in flight),
-// then writes them.  stage_rows alone compiles to load -> s_waitcnt vmcnt(0) -> ds_write per trip (not unrolled: the trip
-// count is a run-time value), i.e. 3.5 serialised memory round trips per image at S = 197: waves spend ~45 % of their
-// cycles in s_waitcnt / s_barrier (SQ_WAIT_ANY, profiles/r02_pmc_attn_*.txt).  Loads are unconditional from clamped rows
-// (a predicated load is merged with its zero fill at once, i.e. waited for); rows past S are zeroed when written.
+// Stage rows [r_begin, r_begin+nrows_pad) of two [S, dh] head slices (global row strides ldgA / ldgB) into two LDS images,
+// zero-filling rows >= S.  Loads batched: every thread first REQUESTS UN 16-byte chunks of each image (2 UN loads in flight),
+// then writes them.  A plain copy loop (one chunk per trip) compiles to load -> s_waitcnt vmcnt(0) -> ds_write per trip (not
+// unrolled: the trip count is a run-time value), i.e. 3.5 serialised memory round trips per image at S = 197: waves spent
+// ~45 % of their cycles in s_waitcnt / s_barrier with it (SQ_WAIT_ANY, profiles/r02_pmc_attn_*.txt).  Loads are unconditional
+// from clamped rows (a predicated load is merged with its zero fill at once, i.e. waited for); rows past S are zeroed when
+// written.
 template <int DH, int UN>
 __device__ __forceinline__ void stage_pair(bf16* imgA, const bf16* baseA, long ldgA, bf16* imgB, const bf16* baseB, long ldgB,
                                            int r_begin, int nrows_pad, int S, int tid) {
@@ -1155,15 +1142,8 @@ inline size_t frame_bwd_lds(int S, int H, int dh) {
   const int spad = (S + 31) / 32 * 32;
   return (size_t)spad * (3 * H * dh + 16) * 2 + (size_t)spad * (H * dh + 16) * 2 + (size_t)2 * H * spad * sizeof(float);
 }
-// Per-frame when the (frame, head) kernels would idle most of their 8 waves: at most 4 query tiles.  IQ_TUNE_ATTN_FRAME=0|1
-// forces the choice where both apply (probes).
-inline bool use_frame(int S, size_t lds) {
-  static const int tune = [] { const char* e = getenv("IQ_TUNE_ATTN_FRAME"); return e ? atoi(e) : -1; }();
-  if (lds > ATT_FRAME_LDS_MAX) return false;
-  if (tune == 0) return false;
-  if (tune == 1) return true;
-  return S <= 128;
-}
+// Per-frame when the (frame, head) kernels would idle most of their 8 waves: at most 4 query tiles.
+inline bool use_frame(int S, size_t lds) { return lds <= ATT_FRAME_LDS_MAX && S <= 128; }
 
 template <int DH>
 int launch_frame_fwd(const void* qkv, void* out, float* lse, int B, int S, int H, hipStream_t st) {
@@ -1235,13 +1215,10 @@ int launch_bwd(const void* qkv, const void* out, const void* dout, const float* 
   return iq_launch_status();
 }
 
-// attn_bwd_once_kernel: dh = 64, no mask, padded length <= 224 rows (one chunk).  Returns its thread count, 0 = not its
-// shape.  IQ_TUNE_ATTN_BWD_ONCE=0|512|1024 turns it off / picks the workgroup size (probes; default 1024).
-inline int once_threads(int S, int dh, bool masked) {
-  static const int tune = [] { const char* e = getenv("IQ_TUNE_ATTN_BWD_ONCE"); return e ? atoi(e) : -1; }();
-  if (masked || dh != 64 || (S + 31) / 32 * 32 > ONCE_MAX_SPAD || tune == 0) return 0;
-  return tune == 512 ? 512 : 1024;
-}
+// attn_bwd_once_kernel: dh = 64, no mask, padded length <= 224 rows (one chunk), 1024 threads (512 measured slower:
+// profiles/attn_bwd_once.txt).
+constexpr int ONCE_THREADS = 1024;
+inline bool use_once(int S, int dh, bool masked) { return !masked && dh == 64 && (S + 31) / 32 * 32 <= ONCE_MAX_SPAD; }
 template <int NT>
 int launch_bwd_once(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int B, int S, int H,
                     hipStream_t st) {
@@ -1318,11 +1295,11 @@ extern "C" int iq_attn_bwd_masked(const void* qkv, const void* out, const void* 
   hipStream_t st = (hipStream_t)stream;
   IQ_PROF(IQ_FAM_ATTN_BWD, st);
   const bool frame = !mask && (dh == 16 || dh == 32 || dh == 64) && use_frame(S, frame_bwd_lds(S, H, dh));
-  const int once = frame ? 0 : once_threads(S, dh, mask != nullptr);
+  const bool once = !frame && use_once(S, dh, mask != nullptr);
   {
     const double rows = (double)B * S, Dm = (double)H * dh;      // qkv, out, dout read; dqkv written; 7 MFMA products
     if (frame) IQ_PROF_K(2.0 * rows * 8.0 * Dm + 4.0 * B * H * S, 14.0 * B * H * (double)S * S * dh, "attn_frame_bwd_kernel<%d>", dh);
-    else if (once) IQ_PROF_K(2.0 * rows * 8.0 * Dm + 4.0 * B * H * S, 10.0 * B * H * (double)S * S * dh, "attn_bwd_once_kernel<%d>", once);   // 5 products
+    else if (once) IQ_PROF_K(2.0 * rows * 8.0 * Dm + 4.0 * B * H * S, 10.0 * B * H * (double)S * S * dh, "attn_bwd_once_kernel<%d>", ONCE_THREADS);   // 5 products
     else IQ_PROF_K(2.0 * rows * 8.0 * Dm + 4.0 * B * H * S, 14.0 * B * H * (double)S * S * dh, "attn_bwd_kernel<%d, %s>", dh, mask ? "true" : "false");
   }
   if (frame) {
@@ -1332,8 +1309,7 @@ extern "C" int iq_attn_bwd_masked(const void* qkv, const void* out, const void* 
       default: return launch_frame_bwd<64>(qkv, out, dout, lse, dqkv, B, S, H, st);
     }
   }
-  if (once == 512) return launch_bwd_once<512>(qkv, out, dout, lse, dqkv, B, S, H, st);
-  if (once) return launch_bwd_once<1024>(qkv, out, dout, lse, dqkv, B, S, H, st);
+  if (once) return launch_bwd_once<ONCE_THREADS>(qkv, out, dout, lse, dqkv, B, S, H, st);
   return mask ? dispatch_bwd<true>(qkv, out, dout, lse, dqkv, mask, mask_hstride, B, S, H, dh, st)
               : dispatch_bwd<false>(qkv, out, dout, lse, dqkv, nullptr, 0, B, S, H, dh, st);
 }

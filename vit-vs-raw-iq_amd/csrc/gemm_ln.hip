@@ -17,7 +17,6 @@
 // LayerNorm statistics are taken from the bf16-ROUNDED Z (what backward re-reads), two-pass (mean, then centred sum
 // of squares) in fp32: lane-local sums -> 2 shuffles across the 4 lane groups that share a row -> one LDS exchange
 // between the two column-half waves.  Same arithmetic as ln_fwd_kernel; results agree to fp32 summation order.
-#include <stdlib.h>
 
 #include "common.h"
 #include "gemm_common.h"
@@ -584,9 +583,8 @@ extern "C" int iq_gemm_bf16_ln(const void* A, int lda, const void* W, int ldw, c
     }
   }
   // Row block: 128, or 64 where 128-row blocks would leave CUs without a workgroup (cfg C: M = 16,640 = 130 blocks of 128
-  // on 256 CUs).  Same K order per row either way: Z / X / statistics are bit-identical.  IQ_TUNE_LN_ROWS forces it (probes).
-  static const int tune_rows = [] { const char* e = getenv("IQ_TUNE_LN_ROWS"); return e ? atoi(e) : 0; }();
-  const bool rows64 = D == 256 || tune_rows == 64 || (tune_rows == 0 && (M + 127) / 128 <= 320);
+  // on 256 CUs).  Same K order per row either way: Z / X / statistics are bit-identical.
+  const bool rows64 = D == 256 || (M + 127) / 128 <= 320;
   IQ_PROF_K(work_bytes, work_flops, "gemm_ln_kernel<%d, %d>", rows64 ? 64 : 128, D);
   switch (D) {
     case 128: return rows64 ? launch<64, 128>(p, st) : launch<128, 128>(p, st);

@@ -20,7 +20,6 @@
 // LayerNorm in the MFMA register layout instead (rows spread over two waves, 96 accumulators + 48 Z registers + 96
 // recomputed xhat live at once) spilled 26-98 registers whatever was tried.  The Z rows are requested behind the last
 // ring stage (counted vmcnt), mean / rstd / gamma wait in LDS from the start of the kernel.
-#include <stdlib.h>
 
 #include "common.h"
 #include "gemm_common.h"
@@ -320,12 +319,8 @@ int launch(const LnBwdParams& p, hipStream_t st) {
 
 // Row block: 128, or 64 where 128-row blocks would leave CUs without a workgroup (cfg C: M = 16,640 = 130 blocks on 256
 // CUs).  dZ / dY do not depend on it (row-local arithmetic); the gamma / beta partial rows are one per block, so the caller
-// sizes and reduces iq_gemm_lnbwd_partial_rows(M) rows.  IQ_TUNE_LNBWD_ROWS forces it (probes).
-inline int lnbwd_block_rows(int M) {
-  static const int tune_rows = [] { const char* e = getenv("IQ_TUNE_LNBWD_ROWS"); return e ? atoi(e) : 0; }();
-  if (tune_rows == 64 || tune_rows == 128) return tune_rows;
-  return (M + 127) / 128 <= 320 ? 64 : 128;
-}
+// sizes and reduces iq_gemm_lnbwd_partial_rows(M) rows.
+inline int lnbwd_block_rows(int M) { return (M + 127) / 128 <= 320 ? 64 : 128; }
 
 }  // namespace
 

@@ -16,7 +16,6 @@
 // ds_read_b128 fragment reads (16 rows x one chunk column per lane group) bank-conflict free.
 // Epilogue: register-only (see gemm_epilogue): C^T accumulators + v_permlane16_swap give each lane 8
 // consecutive columns of a row.
-#include <stdlib.h>
 
 #include "common.h"
 #include "gemm_common.h"
@@ -394,14 +393,9 @@ extern "C" int iq_gemm_bf16_nt(const void* A, int lda, const void* B, int ldb, v
   // last, partly filled round then costs a whole tile time.  cfg C (M = 16,640): FFN1 / gate data gradient = 1,040 tiles of
   // 128 x 128 = 1.35 rounds, the QKV projection 390, the N = 128 data gradient 130.  The 64-row tile streams A once as well
   // (the weight is re-read from L2).  cfg B's launches are 1,182..2,364 tiles and stay on 128 rows (64-row tiles measured
-  // slower there: more weight re-reads per byte of A).  IQ_TUNE_NT_ROWS = 64 | 128 forces the choice (probes).
-  static const int tune_rows = [] { const char* e = getenv("IQ_TUNE_NT_ROWS"); return e ? atoi(e) : 0; }();
-  static const int tune_tiles = [] { const char* e = getenv("IQ_TUNE_NT_TILES"); return e ? atoi(e) : 512; }();
-  int bm = BM;
-  if (async_ok) {
-    const long t128 = (long)((M + 127) / 128) * ((N + bn - 1) / bn);
-    if (tune_rows == 64 || (tune_rows == 0 && t128 < tune_tiles)) bm = 64;
-  }
+  // slower there: more weight re-reads per byte of A).
+  const long t128 = (long)((M + 127) / 128) * ((N + bn - 1) / bn);
+  const int bm = async_ok && t128 < 512 ? 64 : BM;
   p.tiles_m = (M + bm - 1) / bm;
   p.tiles_n = (N + bn - 1) / bn;
   const int grid = p.tiles_m * p.tiles_n;

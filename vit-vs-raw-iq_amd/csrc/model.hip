@@ -16,7 +16,6 @@
 //   every optimizer step), fp32 MFMA accumulation.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
-#include <stdlib.h>
 #include <string.h>
 
 #include <string>
@@ -271,28 +270,28 @@ WsPlan plan_ws(const iq_model* m, int B) {
 // 33.1 but K 1024 62.3 vs 55.7: its 64-row blocks re-stream the 512 KB weight twice as often).
 inline bool use_fused_ln(int D, int K) { return iq_gemm_ln_supported(D, K) && (D <= 192 || K <= 256); }
 
-// The encoder layer from the attention output on as one launch per direction (ffn_chain.hip).  IQ_TUNE_FFN_CHAIN=0|1 forces the
-// choice (probes); IQ_TUNE_FFN_CHAIN_MIN_ROWS moves the threshold.  Measured (same box each, profiles/r03_probes.txt): cfg B
-// (M = 50,432 rows, D 192, F 768, 7 waves of 32 rows per workgroup) 5.72 -> 4.88 ms per step; cfg C (M = 16,640, D 128, F 1024,
-// 5 waves of 16 rows) 1.313 -> 1.191 ms; cfg A (M = 1,280: 16 workgroups) equal -- below 8,192 rows the tiled GEMMs stay.
-inline bool use_ffn_chain(int M, int S, int D, int F) {
-  static const int tune = [] { const char* e = getenv("IQ_TUNE_FFN_CHAIN"); return e ? atoi(e) : -1; }();
-  static const int min_rows = [] { const char* e = getenv("IQ_TUNE_FFN_CHAIN_MIN_ROWS"); return e ? atoi(e) : 8192; }();
-  if (!iq_ffn_chain_supported(S, D, F) || tune == 0) return false;
-  if (tune == 1) return true;
-  return M >= min_rows;
-}
-
-// ... with the attention output projection + norm1 as its first stage (IQ_TUNE_CHAIN_PRE=0: the projection stays a launch of its
-// own) and the next layer's q,k,v projection as its last, the backward launch with the output projection's data gradient behind
-// it (2; 1: without).  3: the backward launch also takes the q,k,v data gradient of the layer above + norm2 backward in front
-// (iq_qkv_dgrad_ffn_chain_bwd).  Measured: cfg B 108.5 us against 68.1 + 39.6, step 4.896 vs 4.876 ms -- that stage moves 134 MB
-// for 11 GFLOP and every workgroup runs it at the same time, it is as HBM-bound inside the launch as outside; on the small
-// geometries a launch less is worth 1 % (cfg C 1.190 -> 1.180 ms, reference default ViT 1.629 -> 1.612).  Default: 3 up to
-// 32,768 rows, 2 above.
-inline int use_chain_pre(int M) {
-  static const int tune = [] { const char* e = getenv("IQ_TUNE_CHAIN_PRE"); return e ? atoi(e) : -1; }();
-  return tune >= 0 ? tune : M <= 32768 ? 3 : 2;
+// A layer's launch route, a function of the geometry alone.  Three outcomes: the tiled GEMM launches; the chain; the chain
+// whose backward launch also takes the q,k,v data gradient of the layer above.
+struct Route {
+  // The encoder layer from the attention output on as one launch per direction (ffn_chain.hip): the attention output
+  // projection + norm1 is its first stage and the next layer's q,k,v projection its last (iq_attn_out_ffn_chain_fwd), the
+  // backward launch has the output projection's data gradient behind it.  Measured (same box each, profiles/r03_probes.txt):
+  // cfg B (M = 50,432 rows, D 192, F 768, 7 waves of 32 rows per workgroup) 5.72 -> 4.88 ms per step; cfg C (M = 16,640,
+  // D 128, F 1024, 5 waves of 16 rows) 1.313 -> 1.191 ms; cfg A (M = 1,280: 16 workgroups) equal -- below 8,192 rows the
+  // tiled GEMMs stay.
+  bool chain;
+  // ... and the backward launch also takes the q,k,v data gradient of the layer above + norm2 backward in front
+  // (iq_qkv_dgrad_ffn_chain_bwd).  Measured: cfg B 108.5 us against 68.1 + 39.6, step 4.896 vs 4.876 ms -- that stage moves
+  // 134 MB for 11 GFLOP and every workgroup runs it at the same time, it is as HBM-bound inside the launch as outside; on
+  // the small geometries a launch less is worth 1 % (cfg C 1.190 -> 1.180 ms, reference default ViT 1.629 -> 1.612).  Up to
+  // 32,768 rows it does, above it does not.
+  bool chain_takes_qkv_dgrad;
+};
+inline Route layer_route(int M, int S, int D, int F) {
+  Route r;
+  r.chain = iq_ffn_chain_supported(S, D, F) && M >= 8192;
+  r.chain_takes_qkv_dgrad = r.chain && M <= 32768;
+  return r;
 }
 
 #define IQ_TRY(expr, what)                                                              \
@@ -499,6 +498,7 @@ extern "C" int iq_model_forward(iq_model_t* m, const float* src, int batch, void
   const iq_model_cfg_t& c = m->c;
   const int D = c.d_model, F = c.ffn_hidden, S = m->S, H = c.n_head, B = batch;
   const int M = B * S, MT = B * m->tok;
+  const Route route = layer_route(M, S, D, F);
   const bool tr = training != 0 && c.drop_prob > 0.f;
   // dropout step: the caller's persistent counter when bound (survives workspace reallocation, starts from a defined
   // value), else a slot of the workspace
@@ -544,8 +544,8 @@ extern "C" int iq_model_forward(iq_model_t* m, const float* src, int batch, void
     const iq_dropout_t dr1 = site(m, seed, step_dev, 1 + 3 * l, tr);
     const iq_dropout_t drh = site(m, seed, step_dev, 2 + 3 * l, tr);
     const iq_dropout_t dr2 = site(m, seed, step_dev, 3 + 3 * l, tr);
-    if (use_ffn_chain(M, S, D, F) && use_chain_pre(M)) {
-      const bool next = l + 1 < c.n_layers && use_chain_pre(M) >= 2;
+    if (route.chain) {
+      const bool next = l + 1 < c.n_layers;
       IQ_TRY(iq_attn_out_ffn_chain_fwd(ws + a.att, m->sh(o.wo), P + o.bo, &dr1, x, P + o.g1, P + o.be1, ws + a.z1, ws + a.x1,
                                        (float*)(ws + a.mean1), (float*)(ws + a.rstd1), m->sh(o.w1), P + o.b1, &drh, ws + a.hid,
                                        m->sh(o.w2), P + o.b2, &dr2, P + o.g2, P + o.be2, 1e-12f, ws + a.z2, ws + a.x2,
@@ -566,25 +566,18 @@ extern "C" int iq_model_forward(iq_model_t* m, const float* src, int batch, void
       IQ_TRY(iq_gemm_bf16_nt(ws + a.att, D, m->sh(o.wo), D, ws + a.z1, D, M, D, D, &e, stream), "out-proj GEMM");
       IQ_TRY(iq_ln_fwd(ws + a.z1, P + o.g1, P + o.be1, ws + a.x1, (float*)(ws + a.mean1), (float*)(ws + a.rstd1), M, D, 1e-12f, stream), "norm1");
     }
-    // ffn + dropout2 + residual + norm2: one launch per layer where a frame's rows fit one workgroup (iq_ffn_chain_fwd: the
-    // hidden activation is consumed from LDS), else FFN1 then FFN2 (+ norm2 in its epilogue where a workgroup owns whole rows)
-    if (use_ffn_chain(M, S, D, F)) {
-      IQ_TRY(iq_ffn_chain_fwd(ws + a.x1, m->sh(o.w1), P + o.b1, &drh, ws + a.hid, m->sh(o.w2), P + o.b2, &dr2, P + o.g2, P + o.be2,
-                              1e-12f, ws + a.z2, ws + a.x2, (float*)(ws + a.mean2), (float*)(ws + a.rstd2), ws + a.gate, B, S, D, F, stream),
-             "ffn chain + norm2");
+    // ffn + dropout2 + residual + norm2: FFN1 then FFN2 (+ norm2 in its epilogue where a workgroup owns whole rows)
+    memset(&e, 0, sizeof(e));
+    e.bias = P + o.b1; e.relu = 1; e.drop = drh;
+    IQ_TRY(iq_gemm_bf16_nt(ws + a.x1, D, m->sh(o.w1), D, ws + a.hid, F, M, F, D, &e, stream), "ffn1 GEMM");
+    if (use_fused_ln(D, F)) {
+      IQ_TRY(iq_gemm_bf16_ln(ws + a.hid, F, m->sh(o.w2), F, P + o.b2, ws + a.x1, D, &dr2, P + o.g2, P + o.be2, 1e-12f,
+                             ws + a.z2, ws + a.x2, (float*)(ws + a.mean2), (float*)(ws + a.rstd2), M, D, F, stream), "ffn2 GEMM + norm2");
     } else {
       memset(&e, 0, sizeof(e));
-      e.bias = P + o.b1; e.relu = 1; e.drop = drh;
-      IQ_TRY(iq_gemm_bf16_nt(ws + a.x1, D, m->sh(o.w1), D, ws + a.hid, F, M, F, D, &e, stream), "ffn1 GEMM");
-      if (use_fused_ln(D, F)) {
-        IQ_TRY(iq_gemm_bf16_ln(ws + a.hid, F, m->sh(o.w2), F, P + o.b2, ws + a.x1, D, &dr2, P + o.g2, P + o.be2, 1e-12f,
-                               ws + a.z2, ws + a.x2, (float*)(ws + a.mean2), (float*)(ws + a.rstd2), M, D, F, stream), "ffn2 GEMM + norm2");
-      } else {
-        memset(&e, 0, sizeof(e));
-        e.bias = P + o.b2; e.drop = dr2; e.residual = ws + a.x1; e.ldr = D;
-        IQ_TRY(iq_gemm_bf16_nt(ws + a.hid, F, m->sh(o.w2), F, ws + a.z2, D, M, D, F, &e, stream), "ffn2 GEMM");
-        IQ_TRY(iq_ln_fwd(ws + a.z2, P + o.g2, P + o.be2, ws + a.x2, (float*)(ws + a.mean2), (float*)(ws + a.rstd2), M, D, 1e-12f, stream), "norm2");
-      }
+      e.bias = P + o.b2; e.drop = dr2; e.residual = ws + a.x1; e.ldr = D;
+      IQ_TRY(iq_gemm_bf16_nt(ws + a.hid, F, m->sh(o.w2), F, ws + a.z2, D, M, D, F, &e, stream), "ffn2 GEMM");
+      IQ_TRY(iq_ln_fwd(ws + a.z2, P + o.g2, P + o.be2, ws + a.x2, (float*)(ws + a.mean2), (float*)(ws + a.rstd2), M, D, 1e-12f, stream), "norm2");
     }
     x = ws + a.x2;
   }
@@ -713,6 +706,10 @@ static int backward_impl(iq_model_t* m, const float* dlogits, const float* denc,
   // whole rows (D = 128 | 192): norm1's in the FFN1 data gradient of the same layer, norm2's in the QKV data gradient of
   // the layer ABOVE (the top layer's comes from the head and keeps the stand-alone kernel).
   const bool fuse1 = iq_gemm_lnbwd_supported(D, F) != 0, fuse2 = iq_gemm_lnbwd_supported(D, 3 * D) != 0;
+  const Route route = layer_route(M, S, D, F);
+  // the one-launch feed-forward backward (ffn_chain.hip), with the output projection's data gradient behind it, where the
+  // forward ran its one-launch counterpart (it left the gate bits)
+  const bool chain = fuse1 && m->last_train_fwd && route.chain;
   bool deferred = false;      // the layer above left its q,k,v data gradient + this layer's norm2 backward to this layer's chain launch
   for (int sidx = (stage_hi > Lr ? Lr : stage_hi); sidx >= 1 && sidx >= stage_lo; --sidx) {
     const int l = sidx - 1;
@@ -740,13 +737,10 @@ static int backward_impl(iq_model_t* m, const float* dlogits, const float* denc,
         {gQKV, 3 * D, xin, D, G + o.wqkv, G + o.bqkv, 3 * D, D}};     // attention.w_q|w_k|w_v
     // the LayerNorm gamma/beta partial rows of this layer ride on the same reduce launch
     const int rows2 = norm2_here ? iq_ln_bwd_partial_rows(M, D) : deferred ? iq_ffn_chain_bwd_partial_rows(M) : iq_gemm_lnbwd_partial_rows(M);
-    // the one-launch feed-forward backward (ffn_chain.hip) where the forward ran its one-launch counterpart (it left the gate bits)
-    const bool chain = fuse1 && m->last_train_fwd && use_ffn_chain(M, S, D, F);
     const int rows1 = chain ? iq_ffn_chain_bwd_partial_rows(M) : fuse1 ? iq_gemm_lnbwd_partial_rows(M) : iq_ln_bwd_partial_rows(M, D);
     const iq_reduce_seg_t lnseg[4] = {{lp2, rows2, 2L * D, G + o.g2, D}, {lp2 + D, rows2, 2L * D, G + o.be2, D},
                                       {lp1, rows1, 2L * D, G + o.g1, D}, {lp1 + D, rows1, 2L * D, G + o.be1, D}};
     const iq_dropout_t dr1 = m->bwd_site(1 + 3 * l, step_dev, tr);
-    const bool post = chain && use_chain_pre(M) >= 2;       // ... and the output projection's data gradient behind it
     if (chain && deferred) {
       const LayerOff& ou = m->L[l + 1];
       const iq_dropout_t dr2b = m->bwd_site(3 + 3 * l, step_dev, tr);
@@ -757,8 +751,8 @@ static int backward_impl(iq_model_t* m, const float* dlogits, const float* denc,
              "qkv dgrad of the layer above + norm2 bwd + ffn chain bwd + norm1 bwd + out-proj dgrad");
     } else if (chain) {
       IQ_TRY(iq_ffn_chain_bwd(dO2, m->sht(o.t_w2), ws + a.gate, dscale, gH, m->sht(o.t_w1), gZ, ws + a.z1, (const float*)(ws + a.mean1),
-                              (const float*)(ws + a.rstd1), P + o.g1, &dr1, gZ1, gY1, lp1, post ? m->sht(o.t_wo) : nullptr,
-                              post ? ws + w.gAtt : nullptr, B, S, D, F, stream), "ffn chain bwd + norm1 bwd (+ out-proj dgrad)");
+                              (const float*)(ws + a.rstd1), P + o.g1, &dr1, gZ1, gY1, lp1, m->sht(o.t_wo), ws + w.gAtt, B, S, D, F, stream),
+             "ffn chain bwd + norm1 bwd + out-proj dgrad");
     } else {
       memset(&e, 0, sizeof(e));
       e.gate = ws + a.hid; e.ldg = F; e.gate_scale = dscale;
@@ -775,7 +769,7 @@ static int backward_impl(iq_model_t* m, const float* dlogits, const float* denc,
                          gZ1, gY1, &dr1, nullptr, nullptr, lp1, accumulate, M, D, stream), "norm1 bwd");
       }
     }
-    if (!post) IQ_TRY(iq_gemm_bf16_nt(dAo, D, m->sht(o.t_wo), D, ws + w.gAtt, D, M, D, D, nullptr, stream), "out-proj dgrad");
+    if (!chain) IQ_TRY(iq_gemm_bf16_nt(dAo, D, m->sht(o.t_wo), D, ws + w.gAtt, D, M, D, D, nullptr, stream), "out-proj dgrad");
     if (rh) {
       // gAtt = d y / d (layer l's attention-core output): its gradient-weighted map and relevance step; below layer 0's
       // attention nothing is needed
@@ -795,7 +789,7 @@ static int backward_impl(iq_model_t* m, const float* dlogits, const float* denc,
     // below, that GEMM overwrites gZ / gY and the norm2 partial rows, which the weight gradients / their reduce still read.
     if (pgrads) IQ_TRY(iq_gemm_bf16_wgrad_grouped(wg, 4, M, wws, w.wgrad_ws_bytes, accumulate, 0, lnseg, 4, stream), "layer weight gradients");
     // ... unless the layer below takes it into its own chain launch (iq_qkv_dgrad_ffn_chain_bwd)
-    deferred = l > 0 && fuse2 && chain && post && use_chain_pre(M) >= 3 && sidx - 1 >= stage_lo;
+    deferred = l > 0 && fuse2 && chain && route.chain_takes_qkv_dgrad && sidx - 1 >= stage_lo;
     if (deferred) continue;
     if (l > 0 && fuse2) {
       const LayerOff& ob = m->L[l - 1];
