@@ -71,7 +71,8 @@ int iq_ln_bwd_partial_rows(int M, int D);
  *   tok>0 : embedding mode, output row = (m/tok)*seq + m%tok + cls_off and pe[(m%tok+cls_off),:]
  *           is added (V/models/encoder.py:42-47).
  *   gate  : v *= (gate[m,n] > 0) ? gate_scale : 0   (ReLU+dropout backward from the saved hidden).
- * K%8==0, N%8==0, lda/ldb/ldc/ldr/ldg in elements and %8==0.
+ * K%8==0, N%8==0, lda/ldb/ldc/ldr/ldg in elements and %8==0 (else IQ_STATUS_UNSUPPORTED).  A, B, C, bias, pe, gate and
+ * residual 16-byte aligned (else IQ_STATUS_ARG): every kernel moves 16-byte vectors.
  * The kernel is chosen from the shape; results do not depend on the choice beyond fp32 summation order:
  *   N%256==0, K%64==0, K>=256 and >= 512 tiles of 256x256 (ViT-Base at its batch): persistent 256x256 tiles
  *   (gemm_big.hip, 0.85-1.19 PFLOP/s); otherwise 128x{128,64} tiles (gemm_nt.hip); K%32!=0: register-staged fallback. */

@@ -151,9 +151,11 @@ def test_gemm_plain_and_bias_relu(L, M, N_, K):
                                     (50432, 576, 192), (50001, 768, 64), (100003, 512, 128), (41472 + 5, 320, 192),
                                     (57344, 256, 160), (49664, 1024, 128), (49663, 1024, 128)])
 def test_gemm_wide_n_many_rows(L, M, N_, K):
-    """Wide N, K <= 192, many rows -- the cfg B FFN1 / QKV / FFN2-dgrad shapes and their neighbours (half column tile at
-    N = 576 / 320, K = 64 / 128 / 160, 100 k rows): ragged M tail, strided A, bias+ReLU,
-    gate, residual, and a dropout mask that depends only on (seed, step, site, element index), not on M."""
+    """Wide N, K <= 192, many rows -- the cfg B FFN1 / QKV / FFN2-dgrad shapes and their neighbours.  Every call here has
+    K % 32 == 0 and K < 256, so it runs the ring kernel gemm_nt_async_kernel: column tile 128 (N = 320 alone, neither a
+    multiple of 128 nor above 512, takes 64), row tile 128 because each shape has at least 512 tiles of 128 rows; the
+    1,000-row call at the end has fewer and takes 64-row tiles.  Ragged M tail, strided A, bias+ReLU, gate, residual, and a
+    dropout mask that depends only on (seed, step, site, element index), not on M or on the row tile."""
     g = torch.Generator(device="cuda").manual_seed(M + N_)
     Abig = bf(torch.randn(M, K + 8, device=dev(), generator=g))
     A = Abig[:, :K]

@@ -1010,7 +1010,7 @@ __global__ __launch_bounds__(NW * 64, 2) void ffn_chain_bwd_kernel(const FfnChai
 #pragma unroll
       for (int ks = 0; ks < KS1; ++ks)
         xf[rg][ks] = have ? *reinterpret_cast<const bf16x8*>(p.dO + rowc[rg] * D + 32 * ks + 8 * fc_kperm(g)) : bf16x8{};
-    load_gate(0);
+    if (have) load_gate(0);                             // (a trailing wave without rows has no gate words: they would lie past the buffer)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
 #pragma unroll

@@ -368,6 +368,8 @@ extern "C" int iq_gemm_bf16_nt(const void* A, int lda, const void* B, int ldb, v
   if (M <= 0 || N <= 0) return IQ_OK;
   if (!A || !B || !C || K <= 0) return IQ_ERR_ARG;
   if ((K % 8) || (N % 8) || (lda % 8) || (ldb % 8) || (ldc % 8)) return IQ_ERR_UNSUPPORTED;
+  // every kernel below, the register-staged one included, moves 8 bf16 (4 fp32) per lane as ONE 16-byte vector
+  if (((uintptr_t)A | (uintptr_t)B | (uintptr_t)C) % 16) return IQ_ERR_ARG;
   GemmParams p = {};
   p.A = (const bf16*)A; p.B = (const bf16*)B; p.C = (bf16*)C;
   p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.M = M; p.N = N; p.K = K;
@@ -382,10 +384,11 @@ extern "C" int iq_gemm_bf16_nt(const void* A, int lda, const void* B, int ldb, v
     p.gate = (const bf16*)epi->gate; p.ldg = epi->ldg; p.gate_scale = epi->gate_scale;
     p.residual = (const bf16*)epi->residual; p.ldr = epi->ldr;
     if ((p.gate && (p.ldg % 8)) || (p.residual && (p.ldr % 8))) return IQ_ERR_UNSUPPORTED;
+    if (((uintptr_t)p.gate | (uintptr_t)p.residual | (uintptr_t)p.pe) % 16) return IQ_ERR_ARG;
   }
   hipStream_t st = (hipStream_t)stream;
   IQ_PROF(IQ_FAM_GEMM_NT, st);
-  const bool async_ok = (K % 32 == 0) && (((uintptr_t)A | (uintptr_t)B) % 16 == 0);
+  const bool async_ok = K % 32 == 0;
   // Column tile: 128 for wide N, else 64 (the register-staged fallback for K % 32 != 0 uses the same choice).
   const bool wide = (N % 128 == 0 || N > 512);
   const int bn = wide ? 128 : 64;
@@ -419,8 +422,7 @@ extern "C" int iq_gemm_bf16_nt(const void* A, int lda, const void* B, int ldb, v
   }
   // C = A W^T + R, nothing else in the tail, whole rows in one 192- / 128-column tile: residual streamed as extra K stages.
   // (the plain 192-column tile reads A once -- N=192 K=768: 27.6 vs 37.3 us -- but lost it all to an exposed residual fetch)
-  if (async_ok && epi_mode == EPI_RES && (N == 192 || N == 128) && K >= 384 && !has_bias && !p.relu && !p.drop_on &&
-      ((uintptr_t)p.residual % 16) == 0) {
+  if (async_ok && epi_mode == EPI_RES && (N == 192 || N == 128) && K >= 384 && !has_bias && !p.relu && !p.drop_on) {
     p.tiles_m = (M + BM - 1) / BM;
     p.tiles_n = 1;
     const size_t lds = (size_t)3 * (BM + N) * 32 * 2;       // <= 60 KiB: under the 64 KiB default cap, no attribute call
