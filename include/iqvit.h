@@ -349,6 +349,40 @@ typedef struct iq_synth {
 int iq_frames_synth(float* raw /*[n,len,2]*/, int64_t* labels, float* snr /*[n], NaN when no noise*/,
                     float* drawn /*NULL or [n,4] = {class, snr_db, phase, power before normalisation}*/,
                     int32_t* symbols /*NULL or [n,len]*/, int n_frames, int len, const iq_synth_t* par, iq_stream_t stream);
+/* Spectrogram front end (csrc/spectrogram.hip): the time-frequency image between the channel above and the ViT, and its adjoint.
+ * x[n_frames, 2, len] fp32 is the planar output of iq_frames_preprocess / iq_frames_impair with take = len (I plane, then Q
+ * plane).  Column t of a frame's image is the transform of the n_fft samples from j0 = t*hop - pad; with j = j0 + m:
+ *   Re[t,k] = sum_m I[j] c[m,k] + Q[j] s[m,k],   Im[t,k] = sum_m Q[j] c[m,k] - I[j] s[m,k],   m = 0 .. n_fft-1,
+ * samples with j outside [0, len) count as zero and are never read.  table is DEVICE fp32 [2, n_fft, n_fft], table[0][m][k] =
+ * c[m,k], table[1][m][k] = s[m,k]: plain numbers to the kernel (spectrogram.py fills it with w[m] cos / sin(2 pi k m / n_fft),
+ * computed in fp64 and rounded).  P = (Re^2 + Im^2) * inv_norm; mode 0: out = P * scale + shift; mode 1: out = log10(P + floor)
+ * * scale + shift, the product and the sum rounded separately (no fused multiply-add).  out[n_frames, 1, n_fft, width]: row r
+ * holds bin k = (r + n_fft/2) mod n_fft (numpy.fft.fftshift order: row 0 is the most negative frequency), column t is contiguous.
+ * Arithmetic: fp32-input MFMA, i.e. per accumulator an fp32 fmaf chain over m in ascending order, for each pair (m, m+1) the
+ * two c (Re: I c; Im: Q c) products before the two s products.  A frame's image depends on neither n_frames nor its position.
+ * iq_frames_spectrogram_bwd: dx[n_frames, 2, len] = the gradient of sum(out * dout) with respect to x; Re / Im are recomputed
+ * from x.  g = dout * scale * inv_norm (mode 1: / (ln 10 * (P + floor))), dRe = 2 Re g, dIm = 2 Im g,
+ *   G_I[t,m] = sum_k dRe[t,k] c[m,k] - dIm[t,k] s[m,k],   G_Q[t,m] = sum_k dRe[t,k] s[m,k] + dIm[t,k] c[m,k]   (k in image-row
+ * order), dx[0][j] = sum of G_I[t, j + pad - t*hop] over the columns t whose window covers j, dx[1][j] likewise from G_Q: a
+ * gather in a fixed order, no atomics, two runs agree bit for bit; samples no window covers get exactly 0.
+ * IQ_STATUS_ARG before any launch: NULL x / table / out / dout / dx / par, len < 1, hop < 1, width < 1, pad < 0, mode outside
+ * {0,1}, a non-finite inv_norm / floor / scale / shift, floor <= 0 in mode 1, x / out / dout / dx not 4-byte or table not
+ * 16-byte aligned.  IQ_STATUS_UNSUPPORTED before any launch: n_fft not a multiple of 32 in [32, 256]; len * 8 bytes above
+ * 64 KB (one workgroup keeps one frame in LDS).  n_frames <= 0: success, nothing is launched. */
+typedef struct iq_spectrogram {
+  int n_fft;      /* window length = number of frequency rows H */
+  int hop;        /* column t's window starts at sample t*hop - pad */
+  int pad;        /* >= 0; samples outside [0,len) count as zero and are never read */
+  int width;      /* number of time columns W */
+  int mode;       /* 0: out = P*scale + shift;  1: out = log10(P + floor)*scale + shift */
+  float inv_norm, floor, scale, shift;   /* P = (Re^2 + Im^2) * inv_norm */
+} iq_spectrogram_t;
+int iq_frames_spectrogram(const float* x /*[n,2,len]*/, const float* table /*DEVICE [2,n_fft,n_fft]*/,
+                          float* out /*[n,1,n_fft,width]*/, int n_frames, int len, const iq_spectrogram_t* par,
+                          iq_stream_t stream);
+int iq_frames_spectrogram_bwd(const float* x, const float* table, const float* dout /*[n,1,n_fft,width]*/,
+                              float* dx /*[n,2,len]*/, int n_frames, int len, const iq_spectrogram_t* par,
+                              iq_stream_t stream);
 int iq_patchify(const float* src, void* patches, int kind, int B, int C, int H, int W, int p, int Kpad,
                 iq_stream_t stream);
 int iq_cls_rows(const float* cls, const float* pe, void* x0, int B, int S, int D, const iq_dropout_t* drop,

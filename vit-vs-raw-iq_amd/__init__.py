@@ -13,6 +13,7 @@ Import name: `vit_vs_raw_iq_amd` (the directory name contains hyphens; the repo-
   adversarial -- FGSM / PGD attacks on the model input and accuracy-versus-epsilon curves
   impairments -- channel impairments on the device (phase, frequency offset, shift, gain, AWGN): augmentation and accuracy curves
   synth     -- labelled synthetic frames made on the device as a keyed stream (FrameSynth, SynthStream, train_on_stream)
+  spectrogram -- spectrogram front end on the device: (B, 2, len) frames -> the (B, 1, n_fft, width) image of the ViT, differentiable
   _native   -- ctypes binding of include/iqvit.h  (libiqvit.so; no fallback)
   ViT.models.amc_transformer / transformer_rawIQ.models.transformer_rawIQ
             -- import paths used by the reference's scripts (hyperparameter_tuning.py:19,37)
@@ -27,10 +28,11 @@ from .relevance import attention_relevance, grad_attention_maps
 from .adversarial import fgsm, pgd, robustness_curve
 from .impairments import Impairments, impair, impair_reference, impairment_curve
 from .synth import FrameSynth, SynthStream, synth_reference, train_on_stream
+from .spectrogram import Spectrogram, spectrogram_reference, spectrogram_reference_bwd
 
 __all__ = ["AMCTransformerViT", "AMCTransformerRawIQ", "EncoderViT", "EncoderRawIQ", "EncoderLayer", "LayerNorm",
            "MultiHeadAttention", "PositionwiseFeedForward", "ScaleDotProductAttention", "PatchEmbedding",
            "SequenceEmbedding", "NativePlan", "IqError", "LIB_PATH", "attention_maps", "attention_rollout",
            "rollout_to_input", "input_gradient", "integrated_gradients", "attention_relevance", "grad_attention_maps", "fgsm",
            "pgd", "robustness_curve", "Impairments", "impair", "impair_reference", "impairment_curve", "FrameSynth",
-           "SynthStream", "synth_reference", "train_on_stream"]
+           "SynthStream", "synth_reference", "train_on_stream", "Spectrogram", "spectrogram_reference", "spectrogram_reference_bwd"]

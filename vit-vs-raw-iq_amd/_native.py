@@ -42,6 +42,11 @@ class Synth(C.Structure):
                 ("stream", C.c_uint32), ("frame_base", C.c_uint64)]
 
 
+class Spectrogram(C.Structure):
+    _fields_ = [("n_fft", C.c_int), ("hop", C.c_int), ("pad", C.c_int), ("width", C.c_int), ("mode", C.c_int),
+                ("inv_norm", C.c_float), ("floor", C.c_float), ("scale", C.c_float), ("shift", C.c_float)]
+
+
 class Epilogue(C.Structure):
     _fields_ = [("bias", C.c_void_p), ("relu", C.c_int), ("pe", C.c_void_p), ("tok", C.c_int), ("seq", C.c_int),
                 ("cls_off", C.c_int), ("drop", Dropout), ("gate", C.c_void_p), ("ldg", C.c_int),
@@ -107,6 +112,8 @@ SIGNATURES = {
     "iq_frames_preprocess": (_I, [_P, _P, _I, _I, _I, C.POINTER(C.c_float), _P]),
     "iq_frames_impair": (_I, [_P, _P, _P, _I, _I, _I, C.POINTER(C.c_float), C.POINTER(Impair), _P]),
     "iq_frames_synth": (_I, [_P, _P, _P, _P, _P, _I, _I, C.POINTER(Synth), _P]),
+    "iq_frames_spectrogram": (_I, [_P, _P, _P, _I, _I, C.POINTER(Spectrogram), _P]),
+    "iq_frames_spectrogram_bwd": (_I, [_P, _P, _P, _P, _I, _I, C.POINTER(Spectrogram), _P]),
     "iq_patchify": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "iq_cls_rows": (_I, [_P, _P, _P, _I, _I, _I, C.POINTER(Dropout), _P]),
     "iq_embed_bwd_gather": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, C.POINTER(Dropout), _I, _P]),

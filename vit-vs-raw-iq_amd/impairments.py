@@ -150,16 +150,34 @@ def _take(layout, length, h, w):
     return take
 
 
-def impair(raw, stats, layout, imp, seed=0, step=0, frame_base=0, h=32, w=64, return_drawn=False):
+def _front_end(spectrogram, layout, length):
+    """The `spectrogram=` argument of an input path: None, or a spectrogram.Spectrogram for frames of `length` samples, which
+    needs layout 'vit' (the launch in front of it then runs with take = len and the image is (B, 1, n_fft, width))."""
+    if spectrogram is None:
+        return None
+    from .spectrogram import Spectrogram
+    if not isinstance(spectrogram, Spectrogram):
+        raise TypeError(f"spectrogram must be a Spectrogram or None, got {type(spectrogram).__name__}")
+    if layout != "vit":
+        raise ValueError(f"a spectrogram is an image: layout must be 'vit', got {layout!r}")
+    if spectrogram.length != length:
+        raise ValueError(f"the spectrogram was built for frames of {spectrogram.length} samples, these have {length}")
+    return spectrogram
+
+
+def impair(raw, stats, layout, imp, seed=0, step=0, frame_base=0, h=32, w=64, return_drawn=False, spectrogram=None):
     """raw: device (B, len, 2) fp32 frames -> the model input, (B, 1, h, w) for layout 'vit' or (B, 2, len) for 'rawiq'; with
-    return_drawn also the fp32 (B, 8) table {theta, f, k, conj, s, g, snr_db, sigma per component} the kernel used."""
+    return_drawn also the fp32 (B, 8) table {theta, f, k, conj, s, g, snr_db, sigma per component} the kernel used.  With
+    `spectrogram` (a spectrogram.Spectrogram; layout 'vit') the whole impaired frame goes through it on the same stream and the
+    result is its (B, 1, n_fft, width) image: h and w are not used."""
     if not isinstance(imp, Impairments):
         raise TypeError(f"imp must be an Impairments, got {type(imp).__name__}")
     if not isinstance(raw, torch.Tensor) or raw.dim() != 3 or raw.shape[2] != 2:
         raise ValueError(f"raw must be a (B, len, 2) tensor, got {tuple(raw.shape) if hasattr(raw, 'shape') else raw!r}")
     st = (C.c_float * 4)(*_stats4(stats))
     B, length = raw.shape[0], raw.shape[1]
-    take = _take(layout, length, h, w)
+    spec = _front_end(spectrogram, layout, length)
+    take = _take(layout, length, h, w) if spec is None else length
     if imp.shift_max >= max(length, 1):
         raise ValueError(f"shift_max {imp.shift_max} must be below the frame length {length}")
     par = imp.struct(seed, step, frame_base)
@@ -172,7 +190,10 @@ def impair(raw, stats, layout, imp, seed=0, step=0, frame_base=0, h=32, w=64, re
     if B > 0:
         N.check(N.lib().iq_frames_impair(raw.data_ptr(), out.data_ptr(), N.ptr(drawn), B, length, take, st, C.byref(par),
                                          torch.cuda.current_stream(raw.device).cuda_stream), "iq_frames_impair")
-    x = out.view(B, 1, h, w) if layout == "vit" else out
+    if spec is not None:
+        x = spec(out)
+    else:
+        x = out.view(B, 1, h, w) if layout == "vit" else out
     return (x, drawn) if return_drawn else x
 
 
@@ -204,13 +225,14 @@ def _fixed(base: Impairments, kind, v):
     return base.replace(**{kind: _number(v, kind)}), 0
 
 
-def impairment_curve(model, raw, labels, stats, kind, values, layout=None, base=None, batch=256, seed=0):
+def impairment_curve(model, raw, labels, stats, kind, values, layout=None, base=None, batch=256, seed=0, spectrogram=None):
     """Top-1 accuracy (float) of `model` on the RAW frames per value of one quantity: kind 'snr_db' (dB), 'phase' (rad), 'cfo'
     (cycles/sample), 'shift' (samples) or 'gain_db' (dB) is fixed at each value, everything else comes from `base` (default:
     nothing else).  Chunks of `batch` frames go through `impair` with frame_base = the chunk's start and step 0, then through an
     eval forward of the plan model(x) uses, so the result does not depend on `batch`; one host synchronisation per value.  A
     fixed shift is a roll of the raw chunk on the device in front of the kernel, which composes with a random shift of `base`.
-    The module's `training` flag is left alone."""
+    The module's `training` flag is left alone.  With `spectrogram` (a spectrogram.Spectrogram whose n_fft x width is the
+    image of the ViT) every impaired frame becomes its spectrogram in front of the model."""
     if kind not in KINDS:
         raise ValueError(f"kind must be one of {KINDS}, got {kind!r}")
     enc, plan_of, K = _resolve(model)
@@ -231,7 +253,11 @@ def impairment_curve(model, raw, labels, stats, kind, values, layout=None, base=
         raise ValueError(f"raw must be a (N, len, 2) tensor, got {tuple(raw.shape) if hasattr(raw, 'shape') else raw!r}")
     n, length = raw.shape[0], raw.shape[1]
     h, w = (geom["img_h"], geom["img_w"]) if own == "vit" else (0, 0)
-    _take(layout, length, h, w)
+    spec = _front_end(spectrogram, layout, length)
+    if spec is None:
+        _take(layout, length, h, w)
+    elif (spec.n_fft, spec.width) != (h, w):
+        raise ValueError(f"the spectrogram is {spec.n_fft}x{spec.width}, the model's image {h}x{w}")
     for _, roll in settings:
         if roll >= max(length, 1):
             raise ValueError(f"shift {roll} must be below the frame length {length}")
@@ -251,7 +277,7 @@ def impairment_curve(model, raw, labels, stats, kind, values, layout=None, base=
                 chunk = raw[i:i + batch]
                 if roll:
                     chunk = torch.roll(chunk, -roll, dims=1)
-                x = enc._expect(impair(chunk, stats, layout, imp, seed=seed, step=0, frame_base=i, h=h, w=w))
+                x = enc._expect(impair(chunk, stats, layout, imp, seed=seed, step=0, frame_base=i, h=h, w=w, spectrogram=spec))
                 correct += (_forward(plan, x).argmax(1) == lab[i:i + batch]).sum()
             out.append(correct.item() / max(1, n))
     return out

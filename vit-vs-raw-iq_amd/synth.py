@@ -32,7 +32,7 @@ import torch
 
 from . import _native as N
 from . import data as D
-from .impairments import Impairments, _flag, _index, _number, _stats4, _take
+from .impairments import Impairments, _flag, _front_end, _index, _number, _stats4, _take
 
 KIND_POINTS, KIND_GMSK, KIND_OQPSK = 0, 1, 2
 SHAPED = {"GMSK": KIND_GMSK, "OQPSK": KIND_OQPSK}
@@ -207,15 +207,21 @@ class SynthStream:
     """Batches of a FrameSynth stream as model input: get(step) makes frames [step * batch, (step + 1) * batch) of `stream` and
     passes them through iq_frames_preprocess (z-score with `stats`, layout 'vit' (B, 1, h, w) or 'rawiq' (B, 2, len)) or, with
     `augment` (an impairments.Impairments), through iq_frames_impair with the synth's seed, step word = `stream` and the same
-    frame_base.  All on the current stream of the device, no host synchronisation."""
+    frame_base.  With `spectrogram` (a spectrogram.Spectrogram; layout 'vit') that launch keeps the whole frame (take = len) and
+    the spectrogram follows: x is its (batch, 1, n_fft, width) image, h and w are not used.  All on the current stream of the
+    device, no host synchronisation."""
 
     def __init__(self, synth: FrameSynth, stats, layout: str, batch: int, h: int = 32, w: int = 64, stream: int = 0,
-                 augment=None):
+                 augment=None, spectrogram=None):
         if not isinstance(synth, FrameSynth):
             raise TypeError(f"synth must be a FrameSynth, got {type(synth).__name__}")
         self.synth, self.layout, self.h, self.w = synth, layout, h, w
         self._stats = (C.c_float * 4)(*_stats4(stats))
-        self.take = _take(layout, synth.length, h, w)
+        self.spectrogram = _front_end(spectrogram, layout, synth.length)
+        if self.spectrogram is None:
+            self.take = _take(layout, synth.length, h, w)
+        else:
+            self.take, self.h, self.w = synth.length, self.spectrogram.n_fft, self.spectrogram.width
         self.batch = _index(batch, "batch", 1, 2 ** 31 - 1)
         self.stream = _index(stream, "stream", 0, 2 ** 32 - 1)
         if augment is not None:
@@ -239,6 +245,8 @@ class SynthStream:
             par = self.augment.struct(self.synth.seed, self.stream, base)
             N.check(N.lib().iq_frames_impair(raw.data_ptr(), out.data_ptr(), None, B, length, self.take, self._stats,
                                              C.byref(par), st), "iq_frames_impair")
+        if self.spectrogram is not None:
+            return self.spectrogram(out), y, z
         return (out.view(B, 1, self.h, self.w) if self.layout == "vit" else out), y, z
 
     def batches(self, count, first_step=0):
