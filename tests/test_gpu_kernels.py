@@ -925,10 +925,11 @@ def test_attention_peaked_softmax_is_stable(L):
 
 @pytest.mark.parametrize("S,H,dh", [(197, 3, 64), (65, 8, 16), (300, 2, 32)])
 def test_attention_deferred_rescale_branch(L, S, H, dh):
-    """The forward raises its running maximum (and rescales the output accumulators) only when a key block's maximum
-    exceeds it by more than 2^8: a data-dependent, rarely taken branch.  Force it late: one key of the LAST block
-    matches one query row so strongly that the maximum jumps by far more than the threshold there -- and, in another
-    frame, a spike in the FIRST block that no later block exceeds (no raise after block 0)."""
+    """A late and an early dominant key under the per-block rescale.  Every forward kernel takes the new running maximum and
+    rescales its output accumulators by alpha = exp2(m_old - m_new) in EVERY key block; the name is from an earlier kernel
+    that raised the maximum only past a threshold.  What the case still exercises: one key of the LAST block matches one
+    query row so strongly that the maximum jumps there (alpha ~ 0 wipes everything accumulated so far) -- and, in another
+    frame, a spike in the FIRST block that no later block exceeds (alpha = 1 from block 1 on, later p tiny)."""
     N = _N()
     Bf, D = 3, H * dh
     g = torch.Generator(device="cuda").manual_seed(S + dh)

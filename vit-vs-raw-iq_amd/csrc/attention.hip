@@ -1264,6 +1264,7 @@ extern "C" int iq_attn_fwd_masked(const void* qkv, void* out, float* lse, const 
   if (B <= 0) return IQ_OK;
   if (!qkv || !out || !lse || S <= 0 || H <= 0) return IQ_ERR_ARG;
   if (mask_hstride != 0 && mask_hstride != (long)S * S) return IQ_ERR_ARG;
+  if (!iq_attn_supported(S, dh)) return IQ_ERR_UNSUPPORTED;      // before anything is recorded or launched
   hipStream_t st = (hipStream_t)stream;
   IQ_PROF(IQ_FAM_ATTN_FWD, st);
   const bool frame = !mask && (dh == 16 || dh == 32 || dh == 64) && use_frame(S, frame_fwd_lds(S, H, dh));
@@ -1292,6 +1293,7 @@ extern "C" int iq_attn_bwd_masked(const void* qkv, const void* out, const void* 
   if (B <= 0) return IQ_OK;
   if (!qkv || !out || !dout || !lse || !dqkv || S <= 0 || H <= 0) return IQ_ERR_ARG;
   if (mask_hstride != 0 && mask_hstride != (long)S * S) return IQ_ERR_ARG;
+  if (!iq_attn_supported(S, dh)) return IQ_ERR_UNSUPPORTED;      // before anything is recorded or launched
   hipStream_t st = (hipStream_t)stream;
   IQ_PROF(IQ_FAM_ATTN_BWD, st);
   const bool frame = !mask && (dh == 16 || dh == 32 || dh == 64) && use_frame(S, frame_bwd_lds(S, H, dh));
