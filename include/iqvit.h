@@ -349,6 +349,57 @@ typedef struct iq_synth {
 int iq_frames_synth(float* raw /*[n,len,2]*/, int64_t* labels, float* snr /*[n], NaN when no noise*/,
                     float* drawn /*NULL or [n,4] = {class, snr_db, phase, power before normalisation}*/,
                     int32_t* symbols /*NULL or [n,len]*/, int n_frames, int len, const iq_synth_t* par, iq_stream_t stream);
+/* Pulse-shaped labelled frames made on the device (csrc/waveform.hip): the transmitter above at `sps` samples per symbol, with a
+ * timing phase and a static multipath channel.  Classes, SNRs, balanced, seed, stream, frame_base, raw, labels and snr are those
+ * of iq_frames_synth; frame j = frame_base + i is again a pure function of (seed, stream, j).  Per frame, in this order:
+ *   1. draw NS symbols, 2. shape them into u[n'], n' = 0 .. len+L-2, 3. pass u through the L-tap channel: v[n], n = 0 .. len-1,
+ *   4. rotate by one carrier phase, 5. divide by sqrt(mean |v|^2 + 1e-12), 6. add complex AWGN; 4 to 6 in the arithmetic of
+ *   iq_frames_synth.
+ * L = n_taps, NS = (len + L - 1 + sps) / sps + span (integer division): the symbol words of a frame; the last few may go unused.
+ * Random numbers: the key, the counter layout, the site IQ_SITE_SYNTH and the word-to-integer mapping (uint64(w) * M) >> 32 of
+ * iq_frames_synth (the shared site is deliberate: see the identity below).
+ *   c = 0xFFFFFFFF: words 0..2 as in iq_frames_synth (theta, class, SNR index); word 3 -> q in [0, n_phase) when timing = 1,
+ *                   else q = 0: the frame's timing phase.
+ *   c = 0xFFFFFFF0 + t, t = 0..3, only when L > 1: (g_re, g_im) of tap 2t = Box-Muller of words (0, 1), of tap 2t+1 = Box-Muller
+ *                   of words (2, 3) (the transform of iq_frames_synth's noise); h_l = ((l == 0 ? los : 0) + tap_sigma[l] g_re,
+ *                   tap_sigma[l] g_im).  With L = 1 nothing is drawn and h_0 = (1, 0).
+ *   c = p < 0x80000000: words 4p .. 4p+3 of the symbol stream; word k is symbol k, k < NS.
+ *   c = 0x80000000 + p: the noise of samples 2p and 2p+1, as in iq_frames_synth.
+ * The shaped signal, with m = n' / sps, r = n' % sps, P = pulse[q], F = fpulse[q]:
+ *   kind 0  a[k] = points[offset + idx_k], idx_k = word k mapped to [0, count); u[n'] = a[m] P[r][0], then fmaf over i = 1 ..
+ *           span-1 ascending with a[m+i] P[r][i], real and imaginary parts separately (the chain starts with a product, not with
+ *           zero);                                                                                    symbols[k] = idx_k
+ *   kind 1  CPM (GMSK): b_k = 2 (word k & 1) - 1; inc[n'] = sum_i b[m+i] F[r][i] in wrapping int32; PHI[n'] = sum_{j <= n'}
+ *           inc[j] mod 2^32; u[n'] = (cos, sin)(pi x), x = (float)(int32)PHI[n'] * 2^-31: the phase is an integer, in units of
+ *           2^-32 turn, until that conversion;                                                        symbols[k] = word k & 1
+ *   kind 2  OQPSK: I_k = word k & 1, Q_k = (word k >> 1) & 1, rails (2 b - 1) / sqrt 2; Re u[n'] = the I rail shaped at n' as in
+ *           kind 0, Im u[n'] = the Q rail shaped at n'' = n' + sps/2 (integer division; m and r of n'');  symbols[k] = 2 I_k + Q_k
+ * Channel, only when L > 1: v[n] = sum_{l < L} h_l u[n + L-1 - l], a complex product per tap, l ascending; L = 1: v = u.
+ * With sps = span = n_phase = 1, pulse = {1.0}, timing = 0, n_taps = 1 and kind-0 classes only, raw, labels and snr are those
+ * of iq_frames_synth for the same seed, stream and frame_base, bit for bit, and symbols[:, :len] are its symbols.
+ * Outputs: drawn: NULL or fp32 [n_frames, 8] = {class, snr_db, theta, mean |v|^2 before the normalisation, q, sum_l |h_l|^2, 0,
+ * 0}; symbols: NULL or int32 [n_frames, NS]; taps: NULL or fp32 [n_frames, 8, 2] = h_l as (re, im), zeros beyond L.
+ * IQ_STATUS_ARG before any launch: what iq_frames_synth refuses; len, sps, span, n_phase or n_taps below 1; timing outside
+ * {0,1}; a kind-0 or kind-2 class with NULL pulse, a kind-1 class with NULL fpulse; a non-finite los; a non-finite or negative
+ * tap_sigma[l < L]; a misaligned pointer.  IQ_STATUS_UNSUPPORTED: sps > 16, span > 32, n_phase > 64, n_taps > 8; len * 8 bytes
+ * above 64 KB; more than IQ_SYNTH_MAX_CLASSES classes or IQ_SYNTH_MAX_SNRS SNR values.  n_frames <= 0: success, no launch. */
+typedef struct iq_waveform {
+  const float* points; const iq_synth_class_t* classes; int n_classes;   /* as iq_synth_t; kinds 0, 1, 2 */
+  const float* snrs_db; int n_snrs; int balanced;
+  uint64_t seed; uint32_t stream; uint64_t frame_base;
+  int sps;                 /* samples per symbol, 1..16 */
+  int span;                /* taps per polyphase branch = pulse length in symbols, 1..32 */
+  int n_phase;             /* timing phases in the tables, 1..64 */
+  int timing;              /* 1: per-frame phase q drawn in [0, n_phase); 0: q = 0 */
+  const float* pulse;      /* DEVICE fp32 [n_phase][sps][span], kinds 0 and 2: plain numbers to the kernel */
+  const int32_t* fpulse;   /* DEVICE int32 [n_phase][sps][span], kind 1: phase increment per sample, units of 2^-32 turn */
+  int n_taps;              /* channel taps L, 1..8; 1: no channel stage, nothing drawn */
+  float los;               /* added to the real part of tap 0 */
+  float tap_sigma[8];      /* per-component standard deviation of tap l */
+} iq_waveform_t;
+int iq_frames_waveform(float* raw /*[n,len,2]*/, int64_t* labels, float* snr, float* drawn /*NULL or [n,8]*/,
+                       int32_t* symbols /*NULL or [n,NS]*/, float* taps /*NULL or [n,8,2]*/, int n_frames, int len,
+                       const iq_waveform_t* par, iq_stream_t stream);
 /* Spectrogram front end (csrc/spectrogram.hip): the time-frequency image between the channel above and the ViT, and its adjoint.
  * x[n_frames, 2, len] fp32 is the planar output of iq_frames_preprocess / iq_frames_impair with take = len (I plane, then Q
  * plane).  Column t of a frame's image is the transform of the n_fft samples from j0 = t*hop - pad; with j = j0 + m:

@@ -13,6 +13,7 @@ Import name: `vit_vs_raw_iq_amd` (the directory name contains hyphens; the repo-
   adversarial -- FGSM / PGD attacks on the model input and accuracy-versus-epsilon curves
   impairments -- channel impairments on the device (phase, frequency offset, shift, gain, AWGN): augmentation and accuracy curves
   synth     -- labelled synthetic frames made on the device as a keyed stream (FrameSynth, SynthStream, train_on_stream)
+  waveform  -- pulse-shaped frames on the device: RRC shaping, true OQPSK, GMSK as CPM, timing phase, multipath (ShapedSynth)
   spectrogram -- spectrogram front end on the device: (B, 2, len) frames -> the (B, 1, n_fft, width) image of the ViT, differentiable
   _native   -- ctypes binding of include/iqvit.h  (libiqvit.so; no fallback)
   ViT.models.amc_transformer / transformer_rawIQ.models.transformer_rawIQ
@@ -28,6 +29,7 @@ from .relevance import attention_relevance, grad_attention_maps
 from .adversarial import fgsm, pgd, robustness_curve
 from .impairments import Impairments, impair, impair_reference, impairment_curve
 from .synth import FrameSynth, SynthStream, synth_reference, train_on_stream
+from .waveform import ShapedSynth, gmsk_table, rrc_table, waveform_reference
 from .spectrogram import Spectrogram, spectrogram_reference, spectrogram_reference_bwd
 
 __all__ = ["AMCTransformerViT", "AMCTransformerRawIQ", "EncoderViT", "EncoderRawIQ", "EncoderLayer", "LayerNorm",
@@ -35,4 +37,5 @@ __all__ = ["AMCTransformerViT", "AMCTransformerRawIQ", "EncoderViT", "EncoderRaw
            "SequenceEmbedding", "NativePlan", "IqError", "LIB_PATH", "attention_maps", "attention_rollout",
            "rollout_to_input", "input_gradient", "integrated_gradients", "attention_relevance", "grad_attention_maps", "fgsm",
            "pgd", "robustness_curve", "Impairments", "impair", "impair_reference", "impairment_curve", "FrameSynth",
-           "SynthStream", "synth_reference", "train_on_stream", "Spectrogram", "spectrogram_reference", "spectrogram_reference_bwd"]
+           "SynthStream", "synth_reference", "train_on_stream", "Spectrogram", "spectrogram_reference", "spectrogram_reference_bwd",
+           "ShapedSynth", "rrc_table", "gmsk_table", "waveform_reference"]

@@ -42,6 +42,14 @@ class Synth(C.Structure):
                 ("stream", C.c_uint32), ("frame_base", C.c_uint64)]
 
 
+class Waveform(C.Structure):
+    _fields_ = [("points", C.c_void_p), ("classes", C.POINTER(SynthClass)), ("n_classes", C.c_int),
+                ("snrs_db", C.POINTER(C.c_float)), ("n_snrs", C.c_int), ("balanced", C.c_int), ("seed", C.c_uint64),
+                ("stream", C.c_uint32), ("frame_base", C.c_uint64), ("sps", C.c_int), ("span", C.c_int), ("n_phase", C.c_int),
+                ("timing", C.c_int), ("pulse", C.c_void_p), ("fpulse", C.c_void_p), ("n_taps", C.c_int), ("los", C.c_float),
+                ("tap_sigma", C.c_float * 8)]
+
+
 class Spectrogram(C.Structure):
     _fields_ = [("n_fft", C.c_int), ("hop", C.c_int), ("pad", C.c_int), ("width", C.c_int), ("mode", C.c_int),
                 ("inv_norm", C.c_float), ("floor", C.c_float), ("scale", C.c_float), ("shift", C.c_float)]
@@ -112,6 +120,7 @@ SIGNATURES = {
     "iq_frames_preprocess": (_I, [_P, _P, _I, _I, _I, C.POINTER(C.c_float), _P]),
     "iq_frames_impair": (_I, [_P, _P, _P, _I, _I, _I, C.POINTER(C.c_float), C.POINTER(Impair), _P]),
     "iq_frames_synth": (_I, [_P, _P, _P, _P, _P, _I, _I, C.POINTER(Synth), _P]),
+    "iq_frames_waveform": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, C.POINTER(Waveform), _P]),
     "iq_frames_spectrogram": (_I, [_P, _P, _P, _I, _I, C.POINTER(Spectrogram), _P]),
     "iq_frames_spectrogram_bwd": (_I, [_P, _P, _P, _P, _I, _I, C.POINTER(Spectrogram), _P]),
     "iq_patchify": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
