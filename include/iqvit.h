@@ -400,6 +400,47 @@ typedef struct iq_waveform {
 int iq_frames_waveform(float* raw /*[n,len,2]*/, int64_t* labels, float* snr, float* drawn /*NULL or [n,8]*/,
                        int32_t* symbols /*NULL or [n,NS]*/, float* taps /*NULL or [n,8,2]*/, int n_frames, int len,
                        const iq_waveform_t* par, iq_stream_t stream);
+/* Receiver for the frames above (csrc/receiver.hip): matched filter, one timing estimate per frame, one sample per symbol.
+ * raw[n_frames, len, 2] fp32, x[n] = raw[n][0] + j raw[n][1], zero outside [0, len).  table G is DEVICE fp32 [n_frac][J+1],
+ * J = sps * span, h = J / 2 (integer division): plain numbers to the kernel (receiver.py fills it with G[f][j] =
+ * p((f / n_frac + h - j) / sps) / sqrt(sps), p the root-raised cosine, zero where the argument leaves the span).  The
+ * interpolating matched filter at time m + f / n_frac (in samples) is
+ *   y(m + f / n_frac) = sum_{j = 0 .. J} x[m + j - h] G[f][j].
+ * Energies: E[r] = sum_{n = r (mod sps), 0 <= n < len} |y(n)|^2, r = 0 .. sps-1 (f = 0 at every sample of the frame).  y(n) is an
+ * fp32-input MFMA product (an fp32 fmaf chain per output), |y|^2 = fmaf(im, im, re * re); the sum over n runs in a fixed order
+ * (lane l of a wave adds n = r + sps (l + 64 i), i ascending, then the wave's butterfly): no atomics, two runs agree bit for bit.
+ * Timing: u in [0, sps * n_frac) is the sampling instant in units of 1 / n_frac sample, r^ = u / n_frac, f^ = u % n_frac.
+ *   IQ_RX_GIVEN        u = par->u[frame] reduced into [0, sps * n_frac) (NULL: 0); est t0 = NaN
+ *   IQ_RX_OERDER_MEYR  X = sum_r E[r] exp(-2 pi j r / sps), t0 = (-arg X * sps / 2 pi) mod sps, u = rint(t0 * n_frac) mod
+ *                      (sps * n_frac); a non-finite t0 gives u = 0.  Needs sps >= 3.
+ *   IQ_RX_ENERGY       u = n_frac * argmax_r E[r], the lowest r on ties (and when no E[r] compares: r = 0); est t0 = r
+ * Symbols: v[k] = y(r^ + f^ / n_frac + k sps), k = 0 .. n_out-1, n_out = len / sps (integer division): an fmaf chain over j
+ * ascending from 0.  normalise = 1: s = v / sqrt(mean_k |v[k]|^2 + 1e-12); 0: s = v.
+ * Outputs: sym[n_frames, n_out, 2] fp32; est: NULL or fp32 [n_frames, 4] = {t0 in samples, u, |X| / sum_r E[r] (0 when the sum
+ * is 0), mean |v|^2}; energy: NULL or fp32 [n_frames, sps].  A frame's outputs depend on neither n_frames nor its position.
+ * iq_frames_receive_bwd: the adjoint with the timing held fixed: u = par->u as in IQ_RX_GIVEN whatever par->mode says (pass the
+ * u of the forward's est).  normalise = 1: dv = (ds - s Re<ds, s> / n_out) / rho, s = the forward's sym, rho = sqrt(est[3] +
+ * 1e-12) from the forward's est (required then); 0: dv = ds, sym and est are not read.  Then
+ *   dx[n] = sum_k dv[k] G[f^][n - k sps - r^ + h], over the k with an index in [0, J], k ascending: a gather, no atomics, two
+ * runs agree bit for bit.  dx[n_frames, len, 2].
+ * IQ_STATUS_ARG before any launch, outputs untouched: NULL raw / sym / dsym / dx / par / table, NULL sym or est in the backward
+ * with normalise = 1, len, sps, span or n_frac below 1, mode outside 0..2, normalise outside {0,1}, raw / sym / dsym / dx not
+ * 8-byte or any other pointer not 4-byte aligned.  IQ_STATUS_UNSUPPORTED: sps > 16, span > 32, n_frac > 64, len * 8 bytes above
+ * 64 KB, len < sps, IQ_RX_OERDER_MEYR with sps < 3.  n_frames <= 0: success, nothing is launched. */
+enum { IQ_RX_GIVEN = 0, IQ_RX_OERDER_MEYR = 1, IQ_RX_ENERGY = 2 };
+typedef struct iq_receiver {
+  int sps;                 /* samples per symbol, 1..16 */
+  int span;                /* matched-filter length in symbols, 1..32: J = sps * span, J + 1 taps */
+  int n_frac;              /* fractional phases in the table, 1..64 */
+  int mode;                /* IQ_RX_* */
+  int normalise;           /* 1: unit mean power per frame */
+  const float* table;      /* DEVICE fp32 [n_frac][J+1] */
+  const int32_t* u;        /* DEVICE int32 [n_frames] or NULL: IQ_RX_GIVEN and the backward */
+} iq_receiver_t;
+int iq_frames_receive(const float* raw /*[n,len,2]*/, float* sym /*[n,len/sps,2]*/, float* est /*NULL or [n,4]*/,
+                      float* energy /*NULL or [n,sps]*/, int n_frames, int len, const iq_receiver_t* par, iq_stream_t stream);
+int iq_frames_receive_bwd(const float* dsym /*[n,len/sps,2]*/, const float* sym, const float* est, float* dx /*[n,len,2]*/,
+                          int n_frames, int len, const iq_receiver_t* par, iq_stream_t stream);
 /* Spectrogram front end (csrc/spectrogram.hip): the time-frequency image between the channel above and the ViT, and its adjoint.
  * x[n_frames, 2, len] fp32 is the planar output of iq_frames_preprocess / iq_frames_impair with take = len (I plane, then Q
  * plane).  Column t of a frame's image is the transform of the n_fft samples from j0 = t*hop - pad; with j = j0 + m:

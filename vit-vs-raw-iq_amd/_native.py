@@ -50,6 +50,11 @@ class Waveform(C.Structure):
                 ("tap_sigma", C.c_float * 8)]
 
 
+class Receiver(C.Structure):
+    _fields_ = [("sps", C.c_int), ("span", C.c_int), ("n_frac", C.c_int), ("mode", C.c_int), ("normalise", C.c_int),
+                ("table", C.c_void_p), ("u", C.c_void_p)]
+
+
 class Spectrogram(C.Structure):
     _fields_ = [("n_fft", C.c_int), ("hop", C.c_int), ("pad", C.c_int), ("width", C.c_int), ("mode", C.c_int),
                 ("inv_norm", C.c_float), ("floor", C.c_float), ("scale", C.c_float), ("shift", C.c_float)]
@@ -121,6 +126,8 @@ SIGNATURES = {
     "iq_frames_impair": (_I, [_P, _P, _P, _I, _I, _I, C.POINTER(C.c_float), C.POINTER(Impair), _P]),
     "iq_frames_synth": (_I, [_P, _P, _P, _P, _P, _I, _I, C.POINTER(Synth), _P]),
     "iq_frames_waveform": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, C.POINTER(Waveform), _P]),
+    "iq_frames_receive": (_I, [_P, _P, _P, _P, _I, _I, C.POINTER(Receiver), _P]),
+    "iq_frames_receive_bwd": (_I, [_P, _P, _P, _P, _I, _I, C.POINTER(Receiver), _P]),
     "iq_frames_spectrogram": (_I, [_P, _P, _P, _I, _I, C.POINTER(Spectrogram), _P]),
     "iq_frames_spectrogram_bwd": (_I, [_P, _P, _P, _P, _I, _I, C.POINTER(Spectrogram), _P]),
     "iq_patchify": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
