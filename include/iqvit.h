@@ -475,6 +475,47 @@ int iq_frames_spectrogram(const float* x /*[n,2,len]*/, const float* table /*DEV
 int iq_frames_spectrogram_bwd(const float* x, const float* table, const float* dout /*[n,1,n_fft,width]*/,
                               float* dx /*[n,2,len]*/, int n_frames, int len, const iq_spectrogram_t* par,
                               iq_stream_t stream);
+/* Cyclic-spectrum front end (csrc/cyclic.hip): the spectral correlation function (SCF) of a frame and its conjugate as square
+ * (cyclic frequency, frequency) images, by the first stage of the FFT accumulation method.  x and table are the spectrogram's:
+ * x[n_frames, 2, len] planar, table DEVICE fp32 [2, Np, Np] = (c, s), Np = n_fft.  rot is DEVICE fp32 [2, Np], rot[0][r] = rc[r],
+ * rot[1][r] = rs[r]: plain numbers to the kernel (cyclic.py fills it with cos / sin(2 pi r / Np), computed in fp64 and rounded).
+ * Window t = 0 .. columns-1 starts at j0 = t*hop - pad; samples outside [0, len) count as zero and are never read.
+ *   X[t,k]  = Re + i Im of the spectrogram entry above
+ *   Y[t,k]  = X[t,k] (rc[r] - i rs[r]),  r = (k * (j0 mod Np)) mod Np, both mods non-negative: the phase of window t referred to
+ *             sample 0.  Yre = fmaf(Xim, rs, Xre * rc), Yim = fmaf(-Xre, rs, Xim * rc).
+ *   S[k,l]  = sum_t Y[t,k] conj(Y[t,l])   (SCF at alpha = f_k - f_l),     Sc[k,l] = sum_t Y[t,k] Y[t,l]   (alpha = f_k + f_l)
+ *   D[k]    = sum_t |Y[t,k]|^2
+ *   P = |S|^2 * inv2 (Pc from Sc likewise), |S|^2 = fmaf(Sim, Sim, Sre * Sre), inv2 = inv_norm * inv_norm rounded to fp32
+ *   mode 0 (power): v = P;  mode 1 (log): v = log10(P + floor);  mode 2 (coherence): v = P / ((D[k] * D[l]) * inv2 + floor), the
+ *   two products and the sum rounded separately.  out = v * scale + shift, product and sum rounded separately.
+ * out[n_frames, C, Np, Np]: row rho holds cyclic bin a = (rho + Np/2) mod Np, column kappa holds channel k = (kappa + Np/2) mod Np
+ * (both in fftshift order); the SCF channel reads l = (k - a) mod Np, the conjugate channel l = (a - k) mod Np.  kind 0: SCF only
+ * (C = 1); 1: conjugate only (C = 1); 2: both (C = 2, SCF first).
+ * Arithmetic: fp32-input MFMA throughout.  X: per accumulator an fp32 fmaf chain over m ascending, for each pair (m, m+1) the
+ * two c products before the two s products, as the spectrogram.  S, Sc: per accumulator an fmaf chain over t ascending from 0,
+ * for each pair (t, t+1) the two Re(l) Re(k) products before the two Im(l) Im(k) products (real parts; SCF adds, the conjugate
+ * subtracts) resp. the two Re(l) Im(k) before the two Im(l) Re(k) products (imaginary parts; SCF subtracts, the conjugate adds).
+ * D[k]: d = fmaf(Yim, Yim, fmaf(Yre, Yre, d)) over t ascending.  No atomics: two runs agree bit for bit, and a frame's image
+ * depends on neither n_frames nor its position.  Nothing is allocated, the host is not synchronised.
+ * IQ_STATUS_ARG before any launch: NULL x / table / rot / out / par, len < 1, hop < 1, columns < 1, pad < 0, kind or mode outside
+ * 0..2, a non-finite inv_norm / floor / scale / shift, floor <= 0 in mode 1 or 2, x / table / rot not 4-byte or out not 16-byte
+ * aligned.  IQ_STATUS_UNSUPPORTED before any launch: n_fft not a multiple of 32 in [32, 256]; len * 8 bytes above 64 KB (one
+ * workgroup keeps one frame in LDS).  Within these the LDS plan holds every case (frame + rot + D + 32 columns of Y: at most
+ * 64 KB + 3 KB + 64.25 KB of 160 KB), so nothing else is refused.  n_frames <= 0: success, nothing is launched.
+ * Launch shape (the image is the same bit for bit): with chunks = ceil(columns / 32), when 4 * (2 len rounded up to 4 + 3 Np +
+ * chunks * 64 (Np + 1) + 64 Np) bytes <= 144 KB one workgroup per frame keeps all of Y in LDS and takes the bands of 32 channels
+ * in turn; otherwise one workgroup per (frame, band) holds 32 columns of Y at a time and recomputes X for its band. */
+typedef struct iq_cyclic {
+  int n_fft;      /* window length Np = image height = image width */
+  int hop;        /* window t starts at sample t*hop - pad */
+  int pad;        /* >= 0 */
+  int columns;    /* number of windows T summed over */
+  int kind;       /* 0: SCF; 1: conjugate SCF; 2: both, SCF first */
+  int mode;       /* 0: power; 1: log; 2: coherence */
+  float inv_norm, floor, scale, shift;
+} iq_cyclic_t;
+int iq_frames_cyclic(const float* x /*[n,2,len]*/, const float* table /*DEVICE [2,n_fft,n_fft]*/, const float* rot /*DEVICE [2,n_fft]*/,
+                     float* out /*[n,C,n_fft,n_fft]*/, int n_frames, int len, const iq_cyclic_t* par, iq_stream_t stream);
 int iq_patchify(const float* src, void* patches, int kind, int B, int C, int H, int W, int p, int Kpad,
                 iq_stream_t stream);
 int iq_cls_rows(const float* cls, const float* pe, void* x0, int B, int S, int D, const iq_dropout_t* drop,
