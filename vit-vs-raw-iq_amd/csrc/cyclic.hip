@@ -9,7 +9,7 @@
 // of them Re and Im of S and of Sc) stay in registers from the first column to the last: wave w of the four owns the l tiles w
 // and w+4.  Time goes through LDS in chunks of 32 columns:
 //   stage 1  D[row = bin][col = t] = sum_m A[bin][m] B[m][t], A = the table (read from L2, 32 consecutive bins per row), B =
-//            the frame in LDS at its sliding index, as in spectrogram.hip; wave w computes the bin tiles w and w+4 of the chunk,
+//            the frame in LDS at its sliding index (channel_step of frames.h); wave w computes the bin tiles w and w+4 of the chunk,
 //            applies rot and writes Y[t][bin] (Re plane, Im plane; row stride Np+1 floats: the store has t on the lane and is
 //            conflict-free, the reads below have the bin on the lane).  Columns at and behind `columns` are written as zeros.
 //   psd      thread b < Np adds |Y[t][b]|^2 of the chunk to its D[b], t ascending.
@@ -23,19 +23,14 @@
 // to HBM are float4s of one image row; no atomics, one writer per element, two runs agree bit for bit.
 #include <math.h>
 
-#include "common.h"
+#include "frames.h"
 #include "iqvit.h"
 #include "prof.h"
 
 namespace {
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-
-constexpr int CY_THREADS = 256;
-constexpr int CY_WAVES = CY_THREADS / IQ_WAVE;
-constexpr int CY_TILE = 32;                       // MFMA tile edge: bins, channels, and the time columns of a chunk
-constexpr int CY_MAX_FFT = 256;
-constexpr int CY_SLOTS = CY_MAX_FFT / CY_TILE / CY_WAVES;   // tiles a wave owns at most: w and w + 4
+constexpr int CY_TILE = FR_TILE;                  // MFMA tile edge: bins, channels, and the time columns of a chunk
+constexpr int CY_SLOTS = FR_MAX_FFT / CY_TILE / FR_WAVES;   // tiles a wave owns at most: w and w + 4
 
 struct CyArgs {
   const float* x;
@@ -47,27 +42,15 @@ struct CyArgs {
   int vec4;            // every frame of x starts 16-byte aligned and has a multiple of 4 floats: float4 staging loads
 };
 
-__host__ __device__ inline int cy_frame_floats(int len) { return (2 * len + 3) & ~3; }
 __host__ __device__ inline int cy_ystride(int n_fft) { return n_fft + 1; }
 __host__ __device__ inline int cy_chunk_floats(int n_fft) { return 2 * CY_TILE * cy_ystride(n_fft); }   // Y [2][32][Np+1]
 // floats of LDS: frame [2][len] | rot [2][Np] | psd [Np] | `chunks` chunks of Y | values [2][Np][32]; with chunks = 0 one chunk
 // whose space the values take over
 __host__ __device__ inline size_t cy_lds_floats(int len, int n_fft, size_t chunks) {
-  const size_t fixed = (size_t)cy_frame_floats(len) + 3 * (size_t)n_fft;
+  const size_t fixed = (size_t)frame_floats(len) + 3 * (size_t)n_fft;
   return chunks ? fixed + chunks * cy_chunk_floats(n_fft) + 2 * (size_t)CY_TILE * n_fft : fixed + cy_chunk_floats(n_fft);
 }
 constexpr size_t CY_LDS_CACHE = 144 * 1024;       // bytes up to which Y is kept whole (the CU has 160 KB)
-
-// accumulator register r of lane half h holds tile row (r & 3) + 8 * (r >> 2) + 4 * h; the column is lane & 31
-__device__ __forceinline__ int acc_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
-
-// First sample of column t's window, clamped to [-n_fft, len]: with m in [0, n_fft) a clamped start gives an index outside
-// [0, len) exactly when the true one is outside.
-__device__ __forceinline__ int window_start(long t, const iq_cyclic_t& p, int len) {
-  long j = t * (long)p.hop - (long)p.pad;
-  j = j < -(long)p.n_fft ? -(long)p.n_fft : j;
-  return (int)(j > (long)len ? (long)len : j);
-}
 
 // j0 mod n_fft of column t, non-negative (j0 = t*hop - pad may be negative)
 __device__ __forceinline__ int window_phase(long t, const iq_cyclic_t& p) {
@@ -75,8 +58,7 @@ __device__ __forceinline__ int window_phase(long t, const iq_cyclic_t& p) {
   return (int)(r < 0 ? r + p.n_fft : r);
 }
 
-// 32 window samples (32*mi ..) of one 32-bin x 32-column tile: 16 steps of two samples, four MFMAs each.
-//   Re += c*I + s*Q,   Im += c*Q - s*I
+// 32 window samples (32*mi ..) of one 32-bin x 32-column tile, the table read from L2: 16 steps of two samples (channel_step)
 __device__ __forceinline__ void channel_block(f32x16& re, f32x16& im, const float* tc, const float* ts, int n, const float* fI,
                                               const float* fQ, int j0, int len, int half) {
   float ac[CY_TILE / 2], as[CY_TILE / 2];
@@ -86,21 +68,12 @@ __device__ __forceinline__ void channel_block(f32x16& re, f32x16& im, const floa
     as[s] = ts[(size_t)(2 * s + half) * n];
   }
 #pragma unroll
-  for (int s = 0; s < CY_TILE / 2; ++s) {
-    const int j = j0 + 2 * s + half;
-    const bool in = (unsigned)j < (unsigned)len;
-    const int jc = in ? j : 0;
-    const float bi = in ? fI[jc] : 0.f, bq = in ? fQ[jc] : 0.f;
-    re = __builtin_amdgcn_mfma_f32_32x32x2f32(ac[s], bi, re, 0, 0, 0);
-    re = __builtin_amdgcn_mfma_f32_32x32x2f32(as[s], bq, re, 0, 0, 0);
-    im = __builtin_amdgcn_mfma_f32_32x32x2f32(ac[s], bq, im, 0, 0, 0);
-    im = __builtin_amdgcn_mfma_f32_32x32x2f32(-as[s], bi, im, 0, 0, 0);
-  }
+  for (int s = 0; s < CY_TILE / 2; ++s) channel_step(re, im, ac[s], as[s], fI, fQ, j0 + 2 * s + half, len);
 }
 
 // CACHED: one workgroup per frame keeps every chunk of Y in LDS and loops over the bands; otherwise one per (frame, band)
 template <bool SCF, bool CONJ, bool CACHED>
-__global__ __launch_bounds__(CY_THREADS) void cyclic_kernel(CyArgs a) {
+__global__ __launch_bounds__(FR_THREADS) void cyclic_kernel(CyArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x, lane = tid & (IQ_WAVE - 1), wave = tid >> 6;
   const int col = lane & 31, half = lane >> 5;
@@ -110,20 +83,13 @@ __global__ __launch_bounds__(CY_THREADS) void cyclic_kernel(CyArgs a) {
   const int nchunks = (int)(((long)T + CY_TILE - 1) / CY_TILE), chunk_floats = cy_chunk_floats(n);
   const float* fI = lds;
   const float* fQ = lds + len;
-  float* rc = lds + cy_frame_floats(len);
+  float* rc = lds + frame_floats(len);
   float* rs = rc + n;
   float* psd = rs + n;
   float* ybase = psd + n;
   float* vals = CACHED ? ybase + (size_t)nchunks * chunk_floats : ybase;   // 2 * n * 32 floats <= one chunk's 2 * 32 * (n + 1)
-  {
-    const float* src = a.x + fi * 2 * len;
-    if (a.vec4) {
-      for (int q = tid; q < len / 2; q += CY_THREADS) reinterpret_cast<float4*>(lds)[q] = reinterpret_cast<const float4*>(src)[q];
-    } else {
-      for (int q = tid; q < 2 * len; q += CY_THREADS) lds[q] = src[q];
-    }
-    for (int q = tid; q < 2 * n; q += CY_THREADS) rc[q] = a.rot[q];
-  }
+  stage_frame(lds, a.x + fi * 2 * len, len, a.vec4, tid);
+  for (int q = tid; q < 2 * n; q += FR_THREADS) rc[q] = a.rot[q];
   constexpr int C = (SCF ? 1 : 0) + (CONJ ? 1 : 0);
   float* img = a.out + (size_t)fi * C * n * n;
   const float inv2 = a.p.inv_norm * a.p.inv_norm;
@@ -141,13 +107,13 @@ __global__ __launch_bounds__(CY_THREADS) void cyclic_kernel(CyArgs a) {
       float* yim = yre + CY_TILE * ys;
       if (produce) {
         const long t = t0 + col;
-        const int jw = window_start(t, a.p, len);
+        const int jw = window_start(t, n, a.p.hop, a.p.pad, len);
         const int ph = window_phase(t, a.p);
         __syncthreads();                                         // frame and rot staged; stage 2 of the previous chunk has read Y
         // ---- stage 1: Y[t][bin] of the chunk, bin tiles wave and wave + 4
 #pragma unroll
         for (int u = 0; u < CY_SLOTS; ++u) {
-          const int bt = wave + CY_WAVES * u;
+          const int bt = wave + FR_WAVES * u;
           if (bt >= nk) break;                                   // wave-uniform
           const float* tc = a.table + CY_TILE * bt + col;        // c[m][32 bt + col]
           const float* ts = tc + (size_t)n * n;
@@ -178,7 +144,7 @@ __global__ __launch_bounds__(CY_THREADS) void cyclic_kernel(CyArgs a) {
       const int steps = (tcols + 1) >> 1;
 #pragma unroll
       for (int u = 0; u < CY_SLOTS; ++u) {
-        const int lt = wave + CY_WAVES * u;
+        const int lt = wave + FR_WAVES * u;
         if (lt >= nk) break;                                     // wave-uniform
         for (int s = 0; s < steps; ++s) {
           const int row = (2 * s + half) * ys;
@@ -207,7 +173,7 @@ __global__ __launch_bounds__(CY_THREADS) void cyclic_kernel(CyArgs a) {
     const float dk = psd[k];
 #pragma unroll
     for (int u = 0; u < CY_SLOTS; ++u) {
-      const int lt = wave + CY_WAVES * u;
+      const int lt = wave + FR_WAVES * u;
       if (lt >= nk) break;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
@@ -216,25 +182,25 @@ __global__ __launch_bounds__(CY_THREADS) void cyclic_kernel(CyArgs a) {
         if (mode == 2) den = __fadd_rn(__fmul_rn(__fmul_rn(dk, psd[l]), inv2), a.p.floor);
         int ch = 0;
         if (SCF) {
-          const float P = fmaf(sim[u][r], sim[u][r], sre[u][r] * sre[u][r]) * inv2;
+          const float P = power(sre[u][r], sim[u][r], inv2);
           const float v = mode == 0 ? P : mode == 1 ? log10f(P + a.p.floor) : P / den;
           int row = k - l + hn;                                  // a = (k - l) mod n, row = (a + n/2) mod n
           row = row < 0 ? row + n : row >= n ? row - n : row;
-          vals[(ch * n + row) * CY_TILE + col] = __fadd_rn(__fmul_rn(v, a.p.scale), a.p.shift);
+          vals[(ch * n + row) * CY_TILE + col] = scale_shift(v, a.p.scale, a.p.shift);
           ++ch;
         }
         if (CONJ) {
-          const float P = fmaf(cim[u][r], cim[u][r], cre[u][r] * cre[u][r]) * inv2;
+          const float P = power(cre[u][r], cim[u][r], inv2);
           const float v = mode == 0 ? P : mode == 1 ? log10f(P + a.p.floor) : P / den;
           int row = k + l + hn;                                  // a = (k + l) mod n
           row = row >= 2 * n ? row - 2 * n : row >= n ? row - n : row;
-          vals[(ch * n + row) * CY_TILE + col] = __fadd_rn(__fmul_rn(v, a.p.scale), a.p.shift);
+          vals[(ch * n + row) * CY_TILE + col] = scale_shift(v, a.p.scale, a.p.shift);
         }
       }
     }
     __syncthreads();
     // image column of channel k0 + 4 g is (k0 + 4 g + n/2) mod n; n/2 and k0 are multiples of 16: four columns never straddle the wrap
-    for (int q = tid; q < C * n * (CY_TILE / 4); q += CY_THREADS) {
+    for (int q = tid; q < C * n * (CY_TILE / 4); q += FR_THREADS) {
       const int g = q & 7, rw = q >> 3;                          // rw = channel * n + image row
       int kc = k0 + 4 * g + hn;
       kc = kc >= n ? kc - n : kc;
@@ -243,19 +209,10 @@ __global__ __launch_bounds__(CY_THREADS) void cyclic_kernel(CyArgs a) {
   }
 }
 
-bool is_finite(float v) { return fabsf(v) < INFINITY; }
-
-template <bool SCF, bool CONJ, bool CACHED>
-void launch_shape(const CyArgs& a, int n_frames, size_t lds, hipStream_t st) {
-  if (lds > 48 * 1024)
-    (void)hipFuncSetAttribute((const void*)cyclic_kernel<SCF, CONJ, CACHED>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  cyclic_kernel<SCF, CONJ, CACHED><<<dim3(n_frames, CACHED ? 1 : a.p.n_fft / CY_TILE), CY_THREADS, lds, st>>>(a);
-}
-
 template <bool SCF, bool CONJ>
 void launch(const CyArgs& a, int n_frames, bool cached, size_t lds, hipStream_t st) {
-  if (cached) launch_shape<SCF, CONJ, true>(a, n_frames, lds, st);
-  else launch_shape<SCF, CONJ, false>(a, n_frames, lds, st);
+  launch_frames(cached ? cyclic_kernel<SCF, CONJ, true> : cyclic_kernel<SCF, CONJ, false>,
+                dim3(n_frames, cached ? 1 : a.p.n_fft / CY_TILE), lds, st, a);
 }
 
 }  // namespace
@@ -269,14 +226,13 @@ extern "C" int iq_frames_cyclic(const float* x, const float* table, const float*
   if (!is_finite(p->inv_norm) || !is_finite(p->floor) || !is_finite(p->scale) || !is_finite(p->shift)) return IQ_ERR_ARG;
   if (p->mode != 0 && !(p->floor > 0.f)) return IQ_ERR_ARG;
   if (((uintptr_t)x & 3) || ((uintptr_t)table & 3) || ((uintptr_t)rot & 3) || ((uintptr_t)out & 15)) return IQ_ERR_ARG;
-  if (p->n_fft < 32 || p->n_fft > CY_MAX_FFT || p->n_fft % 32) return IQ_ERR_UNSUPPORTED;
-  if ((size_t)len * 8 > 64 * 1024) return IQ_ERR_UNSUPPORTED;
+  if (!fft_size_ok(p->n_fft) || !frame_fits(len)) return IQ_ERR_UNSUPPORTED;
   if (n_frames <= 0) return IQ_OK;
   hipStream_t st = (hipStream_t)stream;
   IQ_PROF(IQ_FAM_MISC, st);
   CyArgs a;
   a.x = x; a.table = table; a.rot = rot; a.out = out; a.len = len; a.p = *p;
-  a.vec4 = (len % 2 == 0 && ((uintptr_t)x & 15) == 0) ? 1 : 0;
+  a.vec4 = frame_vec4(x, len);
   const int n = p->n_fft, C = p->kind == 2 ? 2 : 1;
   const size_t chunks = ((size_t)p->columns + CY_TILE - 1) / CY_TILE;
   const bool cached = cy_lds_floats(len, n, chunks) * sizeof(float) <= CY_LDS_CACHE;

@@ -10,19 +10,16 @@
 // sincos of a frequency offset are VALU work under that traffic.
 //
 // Random numbers: philox4x32 of common.h.  key = (seed lo, seed hi ^ frame hi), counter = (c, frame lo, IQ_SITE_IMPAIR, step)
-// with frame = frame_base + blockIdx.x.  c = 0xFFFFFFFF gives the four words the frame's parameters are cut from; c = p gives
-// the four words of the noise of output samples 2p and 2p+1 (two Box-Muller pairs).  Nothing depends on the grid.
+// with frame = frame_base + blockIdx.x (frame_key of frames.h).  c = 0xFFFFFFFF gives the four words the frame's parameters
+// are cut from; c = p gives the noise of output samples 2p and 2p+1 (noise4).  Nothing depends on the grid.
 #include <math.h>
 
-#include "common.h"
+#include "frames.h"
 #include "iqvit.h"
 #include "prof.h"
 
 namespace {
 
-constexpr int IMP_THREADS = 256;
-constexpr int IMP_WAVES = IMP_THREADS / IQ_WAVE;
-constexpr uint32_t IMP_PARAM_CTR = 0xFFFFFFFFu;   // never a sample-pair index: len * 8 <= 64 KB
 constexpr float IMP_INV_TWO_PI = 0.15915494309189533577f;
 
 struct ImpArgs {
@@ -39,8 +36,8 @@ struct ImpArgs {
 __device__ __forceinline__ float draw(float lo, float hi, float u) { return fminf(fmaxf(fmaf(hi - lo, u, lo), lo), hi); }
 
 template <bool NOISE>
-__global__ __launch_bounds__(IMP_THREADS) void frames_impair_kernel(ImpArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];   // [ceil(len/2)][4] the frame (I,Q interleaved), then IMP_WAVES sums
+__global__ __launch_bounds__(FR_THREADS) void frames_impair_kernel(ImpArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];   // [ceil(len/2)][4] the frame (I,Q interleaved), then FR_WAVES sums
   const int tid = threadIdx.x, len = a.len, take = a.take;
   const long fi = blockIdx.x;
   const int nq = (len + 1) >> 1;
@@ -49,7 +46,7 @@ __global__ __launch_bounds__(IMP_THREADS) void frames_impair_kernel(ImpArgs a) {
   // ---- stage the frame, summing |s|^2 in one fixed order whichever load width is used
   const float* src = a.raw + fi * len * 2;
   float pw = 0.f;
-  for (int q = tid; q < nq; q += IMP_THREADS) {
+  for (int q = tid; q < nq; q += FR_THREADS) {
     float4 v;
     if (a.vec4) {
       v = reinterpret_cast<const float4*>(src)[q];
@@ -68,9 +65,9 @@ __global__ __launch_bounds__(IMP_THREADS) void frames_impair_kernel(ImpArgs a) {
 
   // ---- the frame's parameters: every thread derives the same values from the same four words (under the loads' latency)
   const iq_impair_t& im = a.imp;
-  const uint64_t frame = im.frame_base + (uint64_t)fi;
-  const uint32_t k0 = (uint32_t)im.seed, k1 = (uint32_t)(im.seed >> 32) ^ (uint32_t)(frame >> 32), flo = (uint32_t)frame;
-  const u32x4 w = philox4x32(IMP_PARAM_CTR, flo, IQ_SITE_IMPAIR, im.step, k0, k1);
+  const FrameKey key = frame_key(im.seed, im.frame_base, blockIdx.x);
+  const uint32_t k0 = key.k0, k1 = key.k1, flo = key.flo;
+  const u32x4 w = philox4x32(FR_PARAM_CTR, flo, IQ_SITE_IMPAIR, im.step, k0, k1);
   const float theta = draw(im.phase_lo, im.phase_hi, u24(w[0]));
   const float f = draw(im.cfo_lo, im.cfo_hi, u24(w[1]));
   const int k = im.rot90 ? (int)(w[2] & 3u) : 0;
@@ -88,7 +85,7 @@ __global__ __launch_bounds__(IMP_THREADS) void frames_impair_kernel(ImpArgs a) {
   float snr = nanf(""), sig = 0.f;
   if (NOISE) {
     snr = draw(im.snr_db_lo, im.snr_db_hi, (float)(w[3] & 0xFFFFu) * 0x1p-16f);
-    const float P = (g * g) * ((((red[0] + red[1]) + red[2]) + red[3]) / (float)len);
+    const float P = (g * g) * (red_sum(red) / (float)len);
     sig = sqrtf(0.5f * P / powf(10.f, snr / 10.f));
   }
   if (tid == 0 && a.drawn) {
@@ -101,13 +98,9 @@ __global__ __launch_bounds__(IMP_THREADS) void frames_impair_kernel(ImpArgs a) {
   float* oi = a.out + fi * 2 * take;
   float* oq = oi + take;
   const int npair = (take + 1) >> 1;
-  for (int p = tid; p < npair; p += IMP_THREADS) {
+  for (int p = tid; p < npair; p += FR_THREADS) {
     float gn[4] = {0.f, 0.f, 0.f, 0.f};
-    if (NOISE) {
-      const u32x4 z = philox4x32((uint32_t)p, flo, IQ_SITE_IMPAIR, im.step, k0, k1);
-      box_muller(z[0], z[1], gn[0], gn[1]);
-      box_muller(z[2], z[3], gn[2], gn[3]);
-    }
+    if (NOISE) noise4((uint32_t)p, flo, IQ_SITE_IMPAIR, im.step, k0, k1, gn);
     float ri[2], rq[2];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
@@ -146,7 +139,7 @@ __global__ __launch_bounds__(IMP_THREADS) void frames_impair_kernel(ImpArgs a) {
   }
 }
 
-bool range_ok(float lo, float hi) { return lo <= hi && fabsf(lo) < INFINITY && fabsf(hi) < INFINITY && hi - lo < INFINITY; }
+bool range_ok(float lo, float hi) { return lo <= hi && is_finite(lo) && is_finite(hi) && hi - lo < INFINITY; }
 
 }  // namespace
 
@@ -163,7 +156,7 @@ extern "C" int iq_frames_impair(const float* raw, float* out, float* drawn, int 
   if (noise && !range_ok(imp->snr_db_lo, imp->snr_db_hi)) return IQ_ERR_ARG;
   if ((imp->rot90 | imp->conj) & ~1) return IQ_ERR_ARG;
   if (imp->shift_max < 0 || imp->shift_max >= len) return IQ_ERR_ARG;
-  if ((size_t)len * 8 > 64 * 1024) return IQ_ERR_UNSUPPORTED;
+  if (!frame_fits(len)) return IQ_ERR_UNSUPPORTED;
   if (n_frames <= 0) return IQ_OK;
   hipStream_t st = (hipStream_t)stream;
   IQ_PROF(IQ_FAM_MISC, st);
@@ -171,17 +164,11 @@ extern "C" int iq_frames_impair(const float* raw, float* out, float* drawn, int 
   a.raw = raw; a.out = out; a.drawn = drawn; a.len = len; a.take = take;
   a.i_mean = stats[0]; a.i_std = stats[1]; a.q_mean = stats[2]; a.q_std = stats[3];
   a.imp = *imp;
-  a.vec4 = (len % 2 == 0 && ((uintptr_t)raw & 15) == 0) ? 1 : 0;
+  a.vec4 = frame_vec4(raw, len);
   a.st2 = (take % 2 == 0 && ((uintptr_t)out & 7) == 0) ? 1 : 0;
-  const size_t lds = (size_t)((len + 1) / 2) * 16 + IMP_WAVES * sizeof(float);
+  const size_t lds = (size_t)((len + 1) / 2) * 16 + FR_WAVES * sizeof(float);
   const double bytes = (double)n_frames * ((double)len * 8 + 2.0 * take * 4 + (drawn ? 32 : 0));
   IQ_PROF_K(bytes, 0.0, "frames_impair_kernel<%s>", noise ? "true" : "false");
-  if (noise) {
-    if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)frames_impair_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    frames_impair_kernel<true><<<n_frames, IMP_THREADS, lds, st>>>(a);
-  } else {
-    if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)frames_impair_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    frames_impair_kernel<false><<<n_frames, IMP_THREADS, lds, st>>>(a);
-  }
+  launch_frames(noise ? frames_impair_kernel<true> : frames_impair_kernel<false>, n_frames, lds, st, a);
   return iq_launch_status();
 }

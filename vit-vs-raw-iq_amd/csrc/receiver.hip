@@ -1,5 +1,6 @@
 // Receiver for pulse-shaped frames (iq_frames_receive / _bwd, include/iqvit.h): matched filter, one timing estimate per frame,
-// one sample per symbol, and the adjoint with the timing held fixed.  One workgroup per frame, the frame in LDS.
+// one sample per symbol, and the adjoint with the timing held fixed.  One workgroup per frame, the frame in LDS (workgroup
+// size, frame limit, launch and the fixed-order sum of the wave sums: frames.h).
 //
 // Sample-rate pass (E[r], the hot part: len * (J + 1) complex-by-real MACs): a sliding Toeplitz GEMM on the fp32-input MFMA
 // v_mfma_f32_16x16x4_f32, per accumulator an fp32 fmaf chain.  A tile is 16 consecutive outputs; a wave takes 16 tiles (256
@@ -24,20 +25,15 @@
 // any use, so r^ < sps and f^ < n_frac whatever the caller's array holds.
 #include <math.h>
 
-#include "common.h"
+#include "frames.h"
 #include "iqvit.h"
 #include "prof.h"
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
-constexpr int RX_THREADS = 256;
-constexpr int RX_WAVES = RX_THREADS / IQ_WAVE;
 constexpr int RX_TILE = 16;                        // outputs of one MFMA row
 constexpr int RX_GROUP = RX_TILE * RX_TILE;        // outputs of one accumulator pair
 constexpr int RX_MAX_SPS = 16, RX_MAX_SPAN = 32, RX_MAX_FRAC = 64;
-constexpr float RX_TWO_PI = 6.28318530717958647692f;
 
 struct RxArgs {
   const float* raw;     // forward
@@ -66,7 +62,7 @@ __device__ __forceinline__ int wrap_u(int u, int period) {
   return u < 0 ? u + period : u;
 }
 
-__global__ __launch_bounds__(RX_THREADS) void frames_receive_kernel(RxArgs a) {
+__global__ __launch_bounds__(FR_THREADS) void frames_receive_kernel(RxArgs a) {
   // Re plane | Im plane | T words [KP + 16] | table row f^ [J + 4] | |y|^2 [len], later v [n_out][2] | E [16] | red [4] | u, rho
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x, lane = tid & (IQ_WAVE - 1), wave = tid >> 6;
@@ -79,18 +75,18 @@ __global__ __launch_bounds__(RX_THREADS) void frames_receive_kernel(RxArgs a) {
   float* pw = grow + ((J + 4) & ~3);
   float* E = pw + ((max(len, 2 * n_out) + 3) & ~3);
   float* red = E + 16;
-  int* ubox = reinterpret_cast<int*>(red + RX_WAVES);
+  int* ubox = reinterpret_cast<int*>(red + FR_WAVES);
 
   // ---- the frame with its zero extension, and the T words
   const float2* src = reinterpret_cast<const float2*>(a.raw) + fi * len;
-  for (int p = tid; p < P; p += RX_THREADS) {
+  for (int p = tid; p < P; p += FR_THREADS) {
     const int n = p - h;
     float2 v = make_float2(0.f, 0.f);
     if (n >= 0 && n < len) v = src[n];
     xr[skew(p)] = v.x;
     xi[skew(p)] = v.y;
   }
-  for (int q = tid; q < KP + 16; q += RX_THREADS) {
+  for (int q = tid; q < KP + 16; q += FR_THREADS) {
     const int j = q - (RX_TILE - 1);
     tw[q] = (j >= 0 && j <= J) ? a.table[j] : 0.f;
   }
@@ -101,7 +97,7 @@ __global__ __launch_bounds__(RX_THREADS) void frames_receive_kernel(RxArgs a) {
     // ---- |y(n)|^2 into pw: 16 tiles of 16 outputs per wave and step
     const int row = lane & 15, kq = lane >> 4;
     const int groups = (len + RX_GROUP - 1) / RX_GROUP;
-    for (int g = wave; g < groups; g += RX_WAVES) {
+    for (int g = wave; g < groups; g += FR_WAVES) {
       f32x4 re = {0.f, 0.f, 0.f, 0.f}, im = {0.f, 0.f, 0.f, 0.f};
       const int p0 = RX_GROUP * g + RX_TILE * row + kq;      // A: row `row`, k `kq`
       const int q0 = kq - row + (RX_TILE - 1);               // T: k `kq`, column `row`
@@ -125,7 +121,7 @@ __global__ __launch_bounds__(RX_THREADS) void frames_receive_kernel(RxArgs a) {
     }
     __syncthreads();
     // ---- E[r]: wave w the residues w, w + 4, ...
-    for (int r = wave; r < sps; r += RX_WAVES) {
+    for (int r = wave; r < sps; r += FR_WAVES) {
       float s = 0.f;
       for (int n = r + sps * lane; n < len; n += sps * IQ_WAVE) s += pw[n];
       s = wave_sum(s);
@@ -133,7 +129,7 @@ __global__ __launch_bounds__(RX_THREADS) void frames_receive_kernel(RxArgs a) {
     }
     __syncthreads();
     if (a.energy)
-      for (int r = tid; r < sps; r += RX_THREADS) a.energy[fi * sps + r] = E[r];
+      for (int r = tid; r < sps; r += FR_THREADS) a.energy[fi * sps + r] = E[r];
   }
 
   // ---- timing: one thread
@@ -154,7 +150,7 @@ __global__ __launch_bounds__(RX_THREADS) void frames_receive_kernel(RxArgs a) {
     if (a.mode == IQ_RX_GIVEN) {
       u = wrap_u(a.u ? a.u[fi] : 0, period);
     } else if (a.mode == IQ_RX_OERDER_MEYR) {
-      t0 = -atan2f(xim, xre) * (float)sps / RX_TWO_PI;
+      t0 = -atan2f(xim, xre) * (float)sps / FR_TWO_PI;
       if (t0 < 0.f) t0 += (float)sps;
       if (t0 >= (float)sps) t0 -= (float)sps;
       if (fabsf(t0) < INFINITY) u = wrap_u((int)rintf(t0 * (float)a.n_frac), period);
@@ -172,13 +168,13 @@ __global__ __launch_bounds__(RX_THREADS) void frames_receive_kernel(RxArgs a) {
   __syncthreads();
   const int u = ubox[0];
   const int rh = u / a.n_frac, fh = u - rh * a.n_frac;
-  for (int j = tid; j <= J; j += RX_THREADS) grow[j] = a.table[(size_t)fh * (J + 1) + j];
+  for (int j = tid; j <= J; j += FR_THREADS) grow[j] = a.table[(size_t)fh * (J + 1) + j];
   __syncthreads();
 
   // ---- symbols: v[k] = sum_j x[rh + k sps + j - h] G[fh][j]; position p = rh + k sps + j
   float2* vs = reinterpret_cast<float2*>(pw);
   float pv = 0.f;
-  for (int k = tid; k < n_out; k += RX_THREADS) {
+  for (int k = tid; k < n_out; k += FR_THREADS) {
     const int p0 = rh + k * sps;
     float vr = 0.f, vi = 0.f;
     for (int j = 0; j <= J; ++j) {
@@ -193,17 +189,17 @@ __global__ __launch_bounds__(RX_THREADS) void frames_receive_kernel(RxArgs a) {
   pv = wave_sum(pv);
   if (lane == 0) red[wave] = pv;
   __syncthreads();
-  const float mean = (((red[0] + red[1]) + red[2]) + red[3]) / (float)n_out;
+  const float mean = red_sum(red) / (float)n_out;
   const float rs = a.normalise ? 1.f / sqrtf(mean + 1e-12f) : 1.f;
   if (tid == 0 && a.est) a.est[4 * fi + 3] = mean;
   float2* dst = reinterpret_cast<float2*>(a.sym) + fi * n_out;
-  for (int k = tid; k < n_out; k += RX_THREADS) {       // every thread reads back what it wrote
+  for (int k = tid; k < n_out; k += FR_THREADS) {       // every thread reads back what it wrote
     const float2 v = vs[k];
     dst[k] = a.normalise ? make_float2(v.x * rs, v.y * rs) : v;
   }
 }
 
-__global__ __launch_bounds__(RX_THREADS) void frames_receive_bwd_kernel(RxArgs a) {
+__global__ __launch_bounds__(FR_THREADS) void frames_receive_bwd_kernel(RxArgs a) {
   // dv [n_out][2] | table row f^ [J + 4] | red [4]
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x, lane = tid & (IQ_WAVE - 1), wave = tid >> 6;
@@ -214,26 +210,26 @@ __global__ __launch_bounds__(RX_THREADS) void frames_receive_bwd_kernel(RxArgs a
   float* red = grow + ((J + 4) & ~3);
   const int u = wrap_u(a.u ? a.u[fi] : 0, sps * a.n_frac);
   const int rh = u / a.n_frac, fh = u - rh * a.n_frac;
-  for (int j = tid; j <= J; j += RX_THREADS) grow[j] = a.table[(size_t)fh * (J + 1) + j];
+  for (int j = tid; j <= J; j += FR_THREADS) grow[j] = a.table[(size_t)fh * (J + 1) + j];
   const float2* ds = reinterpret_cast<const float2*>(a.dsym) + fi * n_out;
   if (a.normalise) {
     const float2* s = reinterpret_cast<const float2*>(a.fsym) + fi * n_out;
     float dot = 0.f;
-    for (int k = tid; k < n_out; k += RX_THREADS) dot = fmaf(ds[k].y, s[k].y, fmaf(ds[k].x, s[k].x, dot));
+    for (int k = tid; k < n_out; k += FR_THREADS) dot = fmaf(ds[k].y, s[k].y, fmaf(ds[k].x, s[k].x, dot));
     dot = wave_sum(dot);
     if (lane == 0) red[wave] = dot;
     __syncthreads();
-    const float c = (((red[0] + red[1]) + red[2]) + red[3]) / (float)n_out;
+    const float c = red_sum(red) / (float)n_out;
     const float ir = 1.f / sqrtf(a.fest[4 * fi + 3] + 1e-12f);
-    for (int k = tid; k < n_out; k += RX_THREADS)
+    for (int k = tid; k < n_out; k += FR_THREADS)
       dv[k] = make_float2((ds[k].x - s[k].x * c) * ir, (ds[k].y - s[k].y * c) * ir);
   } else {
-    for (int k = tid; k < n_out; k += RX_THREADS) dv[k] = ds[k];
+    for (int k = tid; k < n_out; k += FR_THREADS) dv[k] = ds[k];
   }
   __syncthreads();
   // dx[n] = sum_k dv[k] G[fh][n - k sps - rh + h]: j = i - k sps in [0, J], i = n - rh + h
   float2* dst = reinterpret_cast<float2*>(a.dx) + fi * len;
-  for (int n = tid; n < len; n += RX_THREADS) {
+  for (int n = tid; n < len; n += FR_THREADS) {
     const int i = n - rh + h;                              // >= -(sps - 1)
     int klo = i - J <= 0 ? 0 : (i - J + sps - 1) / sps;
     int khi = i < 0 ? -1 : i / sps;
@@ -255,7 +251,7 @@ int check(const void* in, const void* out, int len, const iq_receiver_t* p) {
   if (p->mode < IQ_RX_GIVEN || p->mode > IQ_RX_ENERGY || (p->normalise & ~1)) return IQ_ERR_ARG;
   if (((uintptr_t)in & 7) || ((uintptr_t)out & 7) || ((uintptr_t)p->table & 3) || ((uintptr_t)p->u & 3)) return IQ_ERR_ARG;
   if (p->sps > RX_MAX_SPS || p->span > RX_MAX_SPAN || p->n_frac > RX_MAX_FRAC) return IQ_ERR_UNSUPPORTED;
-  if ((size_t)len * 8 > 64 * 1024 || len < p->sps) return IQ_ERR_UNSUPPORTED;
+  if (!frame_fits(len) || len < p->sps) return IQ_ERR_UNSUPPORTED;
   return IQ_OK;
 }
 
@@ -287,13 +283,12 @@ extern "C" int iq_frames_receive(const float* raw, float* sym, float* est, float
   a.raw = raw; a.sym = sym; a.est = est; a.energy = energy;
   a.sample_pass = (par->mode != IQ_RX_GIVEN || est || energy) ? 1 : 0;
   const int region = len > 2 * a.n_out ? len : 2 * a.n_out;
-  const size_t lds = ((size_t)2 * a.plane + a.KP + 16 + ((a.J + 4) & ~3) + ((region + 3) & ~3) + 16 + RX_WAVES + 4) * sizeof(float);
+  const size_t lds = ((size_t)2 * a.plane + a.KP + 16 + ((a.J + 4) & ~3) + ((region + 3) & ~3) + 16 + FR_WAVES + 4) * sizeof(float);
   const double groups = (double)((len + RX_GROUP - 1) / RX_GROUP);
   IQ_PROF_K((double)n_frames * ((double)len * 8 + (double)a.n_out * 8),
             (double)n_frames * (a.sample_pass ? groups * a.KP * 2048.0 : 0.0) + (double)n_frames * a.n_out * (a.J + 1) * 4.0,
             "frames_receive_kernel");
-  if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)frames_receive_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  frames_receive_kernel<<<n_frames, RX_THREADS, lds, st>>>(a);
+  launch_frames(frames_receive_kernel, n_frames, lds, st, a);
   return iq_launch_status();
 }
 
@@ -308,10 +303,9 @@ extern "C" int iq_frames_receive_bwd(const float* dsym, const float* sym, const 
   IQ_PROF(IQ_FAM_MISC, st);
   RxArgs a = pack(len, par);
   a.dsym = dsym; a.fsym = sym; a.fest = est; a.dx = dx;
-  const size_t lds = ((size_t)((2 * a.n_out + 3) & ~3) + ((a.J + 4) & ~3) + RX_WAVES) * sizeof(float);
+  const size_t lds = ((size_t)((2 * a.n_out + 3) & ~3) + ((a.J + 4) & ~3) + FR_WAVES) * sizeof(float);
   IQ_PROF_K((double)n_frames * ((double)len * 8 + (double)a.n_out * 16), (double)n_frames * len * (par->span + 1) * 4.0,
             "frames_receive_bwd_kernel");
-  if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)frames_receive_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  frames_receive_bwd_kernel<<<n_frames, RX_THREADS, lds, st>>>(a);
+  launch_frames(frames_receive_bwd_kernel, n_frames, lds, st, a);
   return iq_launch_status();
 }

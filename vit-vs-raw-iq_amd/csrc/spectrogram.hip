@@ -10,7 +10,8 @@
 // The B operand is read from the frame in LDS at its sliding index (no im2col copy); samples outside [0, len) are a select of
 // 0, never a read.  The A operand comes from a 32 x 32 block of c and of s staged in LDS (row stride 33 floats: conflict-free
 // for the forward's row read and for the backward's transposed read); at most 2*256*256*4 B = 512 KB, the table stays in L2.
-// Nothing of size width * n_fft * 2 goes to HBM.
+// Nothing of size width * n_fft * 2 goes to HBM.  The frame staging, the window start, the four-MFMA step, the accumulator
+// layout and the image value are the channelizer stages of frames.h, shared with cyclic.hip.
 //
 // Forward: one workgroup per (frame, 32 image rows), four waves; wave w owns time tiles w and w+4 of every 256 columns, so
 // all four share the table block.  The next block is loaded into registers under the MFMAs of the current one.
@@ -22,20 +23,16 @@
 // only, in program order: no atomics, no dependence on timing, two runs agree bit for bit.
 #include <math.h>
 
-#include "common.h"
+#include "frames.h"
 #include "iqvit.h"
 #include "prof.h"
 
 namespace {
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-
-constexpr int SP_THREADS = 256;
-constexpr int SP_WAVES = SP_THREADS / IQ_WAVE;
-constexpr int SP_TILE = 32;                       // MFMA tile edge: image rows, time columns, window samples per block
+constexpr int SP_TILE = FR_TILE;                  // MFMA tile edge: image rows, time columns, window samples per block
 constexpr int SP_TS = SP_TILE + 1;                // LDS row stride of a staged block and of the G products
 constexpr int SP_BLOCK = 2 * SP_TILE * SP_TS;     // floats of one block: c[32][33] then s[32][33]
-constexpr int SP_DROWS = SP_WAVES * SP_TILE;      // rows of dRe / dIm the backward holds at a time
+constexpr int SP_DROWS = FR_WAVES * SP_TILE;      // rows of dRe / dIm the backward holds at a time
 constexpr float SP_LN10 = 2.30258509299404568402f;
 
 struct SpArgs {
@@ -48,17 +45,6 @@ struct SpArgs {
   iq_spectrogram_t p;
   int vec4;            // every frame of x starts 16-byte aligned and has a multiple of 4 floats: float4 staging loads
 };
-
-__device__ __forceinline__ int frame_floats(int len) { return (2 * len + 3) & ~3; }
-
-// The frame [2][len] (I plane, then Q plane) into LDS, as it lies in memory.
-__device__ __forceinline__ void stage_frame(float* dst, const float* src, int len, int vec4, int tid) {
-  if (vec4) {
-    for (int q = tid; q < len / 2; q += SP_THREADS) reinterpret_cast<float4*>(dst)[q] = reinterpret_cast<const float4*>(src)[q];
-  } else {
-    for (int q = tid; q < 2 * len; q += SP_THREADS) dst[q] = src[q];
-  }
-}
 
 // Element q (of 512) of the block (window samples 32*mi .., image rows 32*ki ..): plane q >> 8, sample (q >> 3) & 31, four
 // consecutive rows from 4 * (q & 7).  Image row r holds bin (r + n_fft/2) mod n_fft; n_fft/2 is a multiple of 16, so four
@@ -74,50 +60,25 @@ __device__ __forceinline__ void block_store(float* blk, int q, float4 v) {
   d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
 }
 
-// First sample of column t's window, clamped to [-n_fft, len]: with m in [0, n_fft) a clamped start gives an index outside
-// [0, len) exactly when the true one is outside.
-__device__ __forceinline__ int window_start(long t, const iq_spectrogram_t& p, int len) {
-  long j = t * (long)p.hop - (long)p.pad;
-  j = j < -(long)p.n_fft ? -(long)p.n_fft : j;
-  return (int)(j > (long)len ? (long)len : j);
-}
-
-// 32 window samples of one 32-bin x 32-column tile: 16 steps of two samples, four MFMAs each.
-//   Re += c*I + s*Q,   Im += c*Q - s*I
+// 32 window samples of one 32-bin x 32-column tile from a staged block: 16 steps of two samples (channel_step)
 __device__ __forceinline__ void tile_block(f32x16& re, f32x16& im, const float* blk, const float* fI, const float* fQ, int j0,
                                            int len, int col, int half) {
 #pragma unroll
   for (int s = 0; s < SP_TILE / 2; ++s) {
     const int mm = 2 * s + half;
-    const float ac = blk[mm * SP_TS + col], as = blk[(SP_TILE + mm) * SP_TS + col];
-    const int j = j0 + mm;
-    const bool in = (unsigned)j < (unsigned)len;
-    const int jc = in ? j : 0;
-    const float bi = in ? fI[jc] : 0.f, bq = in ? fQ[jc] : 0.f;
-    re = __builtin_amdgcn_mfma_f32_32x32x2f32(ac, bi, re, 0, 0, 0);
-    re = __builtin_amdgcn_mfma_f32_32x32x2f32(as, bq, re, 0, 0, 0);
-    im = __builtin_amdgcn_mfma_f32_32x32x2f32(ac, bq, im, 0, 0, 0);
-    im = __builtin_amdgcn_mfma_f32_32x32x2f32(-as, bi, im, 0, 0, 0);
+    channel_step(re, im, blk[mm * SP_TS + col], blk[(SP_TILE + mm) * SP_TS + col], fI, fQ, j0 + mm, len);
   }
 }
-
-// accumulator register r of lane half h holds tile row (r & 3) + 8 * (r >> 2) + 4 * h; the column is lane & 31
-__device__ __forceinline__ int acc_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
-
-__device__ __forceinline__ float power(float re, float im, float inv_norm) { return fmaf(im, im, re * re) * inv_norm; }
 
 __device__ __forceinline__ void store_tile(const f32x16& re, const f32x16& im, float* out_rows, int W, int t,
                                            const iq_spectrogram_t& p, int half) {
   if (t >= W) return;
 #pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const float P = power(re[r], im[r], p.inv_norm);
-    const float v = p.mode ? log10f(P + p.floor) : P;
-    out_rows[(size_t)acc_row(r, half) * W + t] = __fadd_rn(__fmul_rn(v, p.scale), p.shift);
-  }
+  for (int r = 0; r < 16; ++r)
+    out_rows[(size_t)acc_row(r, half) * W + t] = image_value(re[r], im[r], p.inv_norm, p.mode, p.floor, p.scale, p.shift);
 }
 
-__global__ __launch_bounds__(SP_THREADS) void spectrogram_fwd_kernel(SpArgs a) {
+__global__ __launch_bounds__(FR_THREADS) void spectrogram_fwd_kernel(SpArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];   // the frame [2][len], then one table block
   const int tid = threadIdx.x, lane = tid & (IQ_WAVE - 1), wave = tid >> 6;
   const int col = lane & 31, half = lane >> 5;
@@ -130,20 +91,20 @@ __global__ __launch_bounds__(SP_THREADS) void spectrogram_fwd_kernel(SpArgs a) {
   stage_frame(lds, a.x + fi * 2 * len, len, a.vec4, tid);
   float* out_rows = a.out + ((size_t)fi * n + (size_t)SP_TILE * ki) * W;
 
-  for (long tg = 0; tg < W; tg += 2 * SP_WAVES * SP_TILE) {
-    const long ta = tg + SP_TILE * wave, tb = ta + SP_WAVES * SP_TILE;
+  for (long tg = 0; tg < W; tg += 2 * FR_WAVES * SP_TILE) {
+    const long ta = tg + SP_TILE * wave, tb = ta + FR_WAVES * SP_TILE;
     const bool has_a = ta < W, has_b = tb < W;                  // wave-uniform
-    const int ja = window_start(ta + col, a.p, len), jb = window_start(tb + col, a.p, len);
+    const int ja = window_start(ta + col, n, a.p.hop, a.p.pad, len), jb = window_start(tb + col, n, a.p.hop, a.p.pad, len);
     f32x16 re_a = {}, im_a = {}, re_b = {}, im_b = {};
-    float4 pre0 = block_load(a.table, n, 0, ki, tid), pre1 = block_load(a.table, n, 0, ki, tid + SP_THREADS);
+    float4 pre0 = block_load(a.table, n, 0, ki, tid), pre1 = block_load(a.table, n, 0, ki, tid + FR_THREADS);
     for (int mi = 0; mi < nk; ++mi) {
       __syncthreads();                                          // the previous block has been read (first pass: nothing)
       block_store(blk, tid, pre0);
-      block_store(blk, tid + SP_THREADS, pre1);
+      block_store(blk, tid + FR_THREADS, pre1);
       __syncthreads();                                          // block mi (and, first pass, the frame) is in LDS
       if (mi + 1 < nk) {
         pre0 = block_load(a.table, n, mi + 1, ki, tid);
-        pre1 = block_load(a.table, n, mi + 1, ki, tid + SP_THREADS);
+        pre1 = block_load(a.table, n, mi + 1, ki, tid + FR_THREADS);
       }
       if (has_a) tile_block(re_a, im_a, blk, fI, fQ, ja + SP_TILE * mi, len, col, half);
       if (has_b) tile_block(re_b, im_b, blk, fI, fQ, jb + SP_TILE * mi, len, col, half);
@@ -153,7 +114,7 @@ __global__ __launch_bounds__(SP_THREADS) void spectrogram_fwd_kernel(SpArgs a) {
   }
 }
 
-__global__ __launch_bounds__(SP_THREADS) void spectrogram_bwd_kernel(SpArgs a) {
+__global__ __launch_bounds__(FR_THREADS) void spectrogram_bwd_kernel(SpArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];   // frame [2][len] | dRe, dIm [2][128][32] | 4 blocks (then G)
   const int tid = threadIdx.x, lane = tid & (IQ_WAVE - 1), wave = tid >> 6;
   const int col = lane & 31, half = lane >> 5;
@@ -169,16 +130,16 @@ __global__ __launch_bounds__(SP_THREADS) void spectrogram_bwd_kernel(SpArgs a) {
   stage_frame(lds, a.x + fi * 2 * len, len, a.vec4, tid);
   float* dxi = a.dx + fi * 2 * len;
   float* dxq = dxi + len;
-  for (int j = tid; j < len; j += SP_THREADS) dxi[j] = dxq[j] = 0.f;   // thread j % 256 owns sample j from here on
+  for (int j = tid; j < len; j += FR_THREADS) dxi[j] = dxq[j] = 0.f;   // thread j % 256 owns sample j from here on
   const float* dout = a.dout + (size_t)fi * n * W;
 
   for (long t0 = 0; t0 < W; t0 += SP_TILE) {
     const long t = t0 + col;
-    const int jw = window_start(t, a.p, len);
+    const int jw = window_start(t, n, a.p.hop, a.p.pad, len);
     const int tcols = (int)(W - t0 < SP_TILE ? W - t0 : SP_TILE);
-    for (int ks = 0; ks * SP_WAVES < nk; ++ks) {
+    for (int ks = 0; ks * FR_WAVES < nk; ++ks) {
       // ---- recompute Re / Im of image rows 32*ki .. of this column tile, one row tile per wave
-      const int ki = ks * SP_WAVES + wave;
+      const int ki = ks * FR_WAVES + wave;
       const bool has_k = ki < nk;                               // wave-uniform
       f32x16 re = {}, im = {};
       for (int mi = 0; mi < nk; ++mi) {
@@ -202,16 +163,16 @@ __global__ __launch_bounds__(SP_THREADS) void spectrogram_bwd_kernel(SpArgs a) {
           dim[(SP_TILE * wave + row) * SP_TILE + col] = 2.f * im[r] * g;
         }
       }
-      const int nkv = nk - ks * SP_WAVES < SP_WAVES ? nk - ks * SP_WAVES : SP_WAVES;   // row tiles held in dre / dim
-      for (int ms = 0; ms * SP_WAVES < nk; ++ms) {
+      const int nkv = nk - ks * FR_WAVES < FR_WAVES ? nk - ks * FR_WAVES : FR_WAVES;   // row tiles held in dre / dim
+      for (int ms = 0; ms * FR_WAVES < nk; ++ms) {
         // ---- G_I[m][t] = sum_k c dRe - s dIm,  G_Q[m][t] = sum_k s dRe + c dIm: one 32-sample segment per wave
-        const int mi = ms * SP_WAVES + wave;
+        const int mi = ms * FR_WAVES + wave;
         const bool has_m = mi < nk;                             // wave-uniform
         f32x16 gi = {}, gq = {};
         for (int kk = 0; kk < nkv; ++kk) {
           __syncthreads();                                      // dre / dim written; G of the previous step gathered
           if (has_m)
-            for (int q = lane; q < 512; q += IQ_WAVE) block_store(blk, q, block_load(a.table, n, mi, ks * SP_WAVES + kk, q));
+            for (int q = lane; q < 512; q += IQ_WAVE) block_store(blk, q, block_load(a.table, n, mi, ks * FR_WAVES + kk, q));
           __syncthreads();
           if (has_m) {
 #pragma unroll
@@ -236,12 +197,12 @@ __global__ __launch_bounds__(SP_THREADS) void spectrogram_bwd_kernel(SpArgs a) {
         }
         __syncthreads();
         // ---- overlap-add: sample j takes G[m][t] of every column t of the tile with m = j + pad - t*hop in this segment group
-        const long mlo = (long)ms * SP_WAVES * SP_TILE;
-        const long mhi = mlo + SP_WAVES * SP_TILE < n ? mlo + SP_WAVES * SP_TILE : (long)n;
+        const long mlo = (long)ms * FR_WAVES * SP_TILE;
+        const long mhi = mlo + FR_WAVES * SP_TILE < n ? mlo + FR_WAVES * SP_TILE : (long)n;
         long jlo = t0 * hop - pad + mlo, jhi = (t0 + tcols - 1) * hop - pad + mhi - 1;   // first and last sample touched
         jlo = jlo < 0 ? 0 : jlo;
         jhi = jhi > len - 1 ? len - 1 : jhi;
-        for (long j = jlo + ((tid - jlo) & (SP_THREADS - 1)); j <= jhi; j += SP_THREADS) {
+        for (long j = jlo + ((tid - jlo) & (FR_THREADS - 1)); j <= jhi; j += FR_THREADS) {
           float si = 0.f, sq = 0.f;
           for (int c = 0; c < tcols; ++c) {
             const long m = j + pad - (t0 + c) * hop;
@@ -259,8 +220,6 @@ __global__ __launch_bounds__(SP_THREADS) void spectrogram_bwd_kernel(SpArgs a) {
   }
 }
 
-bool is_finite(float v) { return fabsf(v) < INFINITY; }
-
 // -> IQ_OK or the refusal; nothing is launched and no pointer dereferenced (other than par) before this returns IQ_OK
 int check(const void* x, const void* table, const void* io_a, const void* io_b, int len, const iq_spectrogram_t* p) {
   if (!x || !table || !io_a || !io_b || !p) return IQ_ERR_ARG;
@@ -268,15 +227,14 @@ int check(const void* x, const void* table, const void* io_a, const void* io_b, 
   if (!is_finite(p->inv_norm) || !is_finite(p->floor) || !is_finite(p->scale) || !is_finite(p->shift)) return IQ_ERR_ARG;
   if (p->mode == 1 && !(p->floor > 0.f)) return IQ_ERR_ARG;
   if (((uintptr_t)x & 3) || ((uintptr_t)table & 15) || ((uintptr_t)io_a & 3) || ((uintptr_t)io_b & 3)) return IQ_ERR_ARG;
-  if (p->n_fft < 32 || p->n_fft > 256 || p->n_fft % 32) return IQ_ERR_UNSUPPORTED;
-  if ((size_t)len * 8 > 64 * 1024) return IQ_ERR_UNSUPPORTED;
+  if (!fft_size_ok(p->n_fft) || !frame_fits(len)) return IQ_ERR_UNSUPPORTED;
   return IQ_OK;
 }
 
 SpArgs pack(const float* x, const float* table, int len, const iq_spectrogram_t* p) {
   SpArgs a;
   a.x = x; a.table = table; a.out = nullptr; a.dout = nullptr; a.dx = nullptr; a.len = len; a.p = *p;
-  a.vec4 = (len % 2 == 0 && ((uintptr_t)x & 15) == 0) ? 1 : 0;
+  a.vec4 = frame_vec4(x, len);
   return a;
 }
 
@@ -292,11 +250,10 @@ extern "C" int iq_frames_spectrogram(const float* x, const float* table, float* 
   SpArgs a = pack(x, table, len, par);
   a.out = out;
   const int n = par->n_fft;
-  const size_t lds = ((size_t)((2 * len + 3) & ~3) + SP_BLOCK) * sizeof(float);
+  const size_t lds = ((size_t)frame_floats(len) + SP_BLOCK) * sizeof(float);
   const double cols = (double)n_frames * par->width;
   IQ_PROF_K((double)n_frames * len * 8 + cols * n * 4 + 8.0 * n * n, 8.0 * cols * n * n, "spectrogram_fwd_kernel");
-  if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)spectrogram_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  spectrogram_fwd_kernel<<<dim3(n_frames, n / SP_TILE), SP_THREADS, lds, st>>>(a);
+  launch_frames(spectrogram_fwd_kernel, dim3(n_frames, n / SP_TILE), lds, st, a);
   return iq_launch_status();
 }
 
@@ -310,10 +267,9 @@ extern "C" int iq_frames_spectrogram_bwd(const float* x, const float* table, con
   SpArgs a = pack(x, table, len, par);
   a.dout = dout; a.dx = dx;
   const int n = par->n_fft;
-  const size_t lds = ((size_t)((2 * len + 3) & ~3) + 2 * SP_DROWS * SP_TILE + SP_WAVES * SP_BLOCK) * sizeof(float);
+  const size_t lds = ((size_t)frame_floats(len) + 2 * SP_DROWS * SP_TILE + FR_WAVES * SP_BLOCK) * sizeof(float);
   const double cols = (double)n_frames * par->width;
   IQ_PROF_K((double)n_frames * len * 16 + cols * n * 4 + 8.0 * n * n, 16.0 * cols * n * n, "spectrogram_bwd_kernel");
-  if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)spectrogram_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  spectrogram_bwd_kernel<<<n_frames, SP_THREADS, lds, st>>>(a);
+  launch_frames(spectrogram_bwd_kernel, n_frames, lds, st, a);
   return iq_launch_status();
 }

@@ -2,8 +2,9 @@
 // `sps` samples per symbol -- a polyphase FIR over the symbols (any pulse: the tables are plain numbers, waveform.py fills them
 // with a root-raised cosine), true OQPSK (the Q rail half a symbol late), CPM from an integer phase-increment table (GMSK), one
 // timing phase per frame, and a static multipath channel of up to 8 taps (tap 0 Rician, the rest Rayleigh) between the shaping
-// and the carrier phase.  The tail -- carrier phase, unit power, AWGN, store -- is frames_synth_kernel's, expression for
-// expression: with sps = span = n_phase = 1, a pulse of 1.0 and one tap the frames are those of iq_frames_synth, bit for bit.
+// and the carrier phase.  The keying, the class / SNR draw, the rotation and the tail (unit power, AWGN, store) are the
+// functions of frames.h that frames_synth_kernel calls: with sps = span = n_phase = 1, a pulse of 1.0 and one tap the frames
+// are those of iq_frames_synth, bit for bit.
 //
 // One workgroup per frame, the frame in LDS.
 //   1. symbol words -> integers in LDS (NS of them, 4 per Philox call) and, if asked for, to `symbols`; the frame's slice
@@ -15,7 +16,7 @@
 //      barrier, every thread writes the rotated v[n] over u[n].  Round k writes [256 k, 256 k + 256) and reads up to
 //      256 k + 255 + L - 1: no round reads what an earlier one wrote, and the barrier of round k + 1 comes after every read of
 //      round k.  With L = 1 there is no barrier and nothing but the rotation.
-//   4. power, normalisation, noise, one 16-byte store per two samples: as synth.hip
+//   4. power, normalisation, noise, one 16-byte store per two samples: frame_scale + store_frame
 // Every LDS index is below NS (symbols: the largest is (len + L - 2 + sps/2) / sps + span - 1 <= NS - 1), below len + L - 1
 // (frame) or below sps * span (table) by construction.
 //
@@ -24,21 +25,16 @@
 // 2t and 2t + 1, c = p < 0x80000000 symbol words 4p..4p+3, c = 0x80000000 + p the noise of samples 2p and 2p + 1.
 #include <math.h>
 
-#include "common.h"
+#include "frames.h"
 #include "iqvit.h"
 #include "prof.h"
 
 namespace {
 
-constexpr int WF_THREADS = 256;
-constexpr int WF_WAVES = WF_THREADS / IQ_WAVE;
 constexpr int WF_MAX_SPS = 16, WF_MAX_SPAN = 32, WF_MAX_PHASE = 64, WF_MAX_TAPS = 8;
 constexpr int WF_POINTS_LDS = 1024;               // a constellation up to this size is read from LDS, a larger one from memory
-constexpr uint32_t WF_PARAM_CTR = 0xFFFFFFFFu;
 constexpr uint32_t WF_TAP_CTR = 0xFFFFFFF0u;      // .. 0xFFFFFFF3: never a symbol or noise group (len * 8 <= 64 KB)
 constexpr uint32_t WF_NOISE_CTR = 0x80000000u;
-constexpr float WF_TWO_PI = 6.28318530717958647692f;
-constexpr float WF_RSQRT2 = 0.70710678118654752440f;
 
 struct WfArgs {
   float* raw;
@@ -65,7 +61,7 @@ struct WfArgs {
 static_assert(sizeof(WfArgs) <= 4096, "kernel arguments");
 
 template <bool NOISE>
-__global__ __launch_bounds__(WF_THREADS) void frames_waveform_kernel(WfArgs a) {
+__global__ __launch_bounds__(FR_THREADS) void frames_waveform_kernel(WfArgs a) {
   // [nq][4] the frame (I,Q interleaved), len + L - 1 samples | [nw][4] the symbols as integers | [sps][span] the table slice |
   // the constellation | 8 taps | wave sums
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -73,7 +69,6 @@ __global__ __launch_bounds__(WF_THREADS) void frames_waveform_kernel(WfArgs a) {
   const long fi = blockIdx.x;
   const int L = a.n_taps, sps = a.sps, span = a.span, ns = a.ns;
   const int nu = len + L - 1;             // shaped samples
-  const int nq = (len + 1) >> 1;          // sample pairs of the output
   const int nw = (ns + 3) >> 2;           // Philox calls of the symbol stream
   const int nt = sps * span;
   float2* fr = reinterpret_cast<float2*>(lds);
@@ -82,21 +77,15 @@ __global__ __launch_bounds__(WF_THREADS) void frames_waveform_kernel(WfArgs a) {
   float2* pts = reinterpret_cast<float2*>(tab + ((nt + 3) & ~3));
   float2* h = pts + a.npts;
   float* red = reinterpret_cast<float*>(h + WF_MAX_TAPS);
-  uint32_t* wsum = reinterpret_cast<uint32_t*>(red + WF_WAVES);
+  uint32_t* wsum = reinterpret_cast<uint32_t*>(red + FR_WAVES);
 
   // ---- the frame's parameters: every thread derives the same values from the same four words
-  const uint64_t frame = a.frame_base + (uint64_t)fi;
-  const uint32_t k0 = (uint32_t)a.seed, k1 = (uint32_t)(a.seed >> 32) ^ (uint32_t)(frame >> 32), flo = (uint32_t)frame;
-  const u32x4 par = philox4x32(WF_PARAM_CTR, flo, IQ_SITE_SYNTH, a.stream, k0, k1);
+  const FrameKey key = frame_key(a.seed, a.frame_base, blockIdx.x);
+  const uint32_t k0 = key.k0, k1 = key.k1, flo = key.flo;
+  const u32x4 par = philox4x32(FR_PARAM_CTR, flo, IQ_SITE_SYNTH, a.stream, k0, k1);
   const float turn = u24(par[0]);
-  int cls, si = 0;
-  if (a.balanced) {
-    cls = (int)(frame % (uint64_t)a.n_classes);
-    if (NOISE) si = (int)((frame / (uint64_t)a.n_classes) % (uint64_t)a.n_snrs);
-  } else {
-    cls = (int)__umulhi(par[1], (uint32_t)a.n_classes);
-    if (NOISE) si = (int)__umulhi(par[2], (uint32_t)a.n_snrs);
-  }
+  int cls, si;
+  draw_class_snr(key.frame, par, a.balanced, a.n_classes, a.n_snrs, NOISE, cls, si);
   const int q = a.timing ? (int)__umulhi(par[3], (uint32_t)a.n_phase) : 0;
   const iq_synth_class_t cd = a.classes[cls];
   const int kind = cd.kind;               // frame-uniform: no branch below diverges
@@ -105,7 +94,7 @@ __global__ __launch_bounds__(WF_THREADS) void frames_waveform_kernel(WfArgs a) {
   sincospif(2.f * turn, &s0, &c0);
 
   // ---- symbol words -> integers in LDS: the constellation index, the bit, 2 I + Q
-  for (int p = tid; p < nw; p += WF_THREADS) {
+  for (int p = tid; p < nw; p += FR_THREADS) {
     const u32x4 z = philox4x32((uint32_t)p, flo, IQ_SITE_SYNTH, a.stream, k0, k1);
     int4 v;
     if (kind == 0) {
@@ -131,10 +120,10 @@ __global__ __launch_bounds__(WF_THREADS) void frames_waveform_kernel(WfArgs a) {
   {
     const uint32_t* src = kind == 1 ? reinterpret_cast<const uint32_t*>(a.fpulse) : reinterpret_cast<const uint32_t*>(a.pulse);
     src += (size_t)q * nt;
-    for (int i = tid; i < nt; i += WF_THREADS) reinterpret_cast<uint32_t*>(tab)[i] = src[i];
+    for (int i = tid; i < nt; i += FR_THREADS) reinterpret_cast<uint32_t*>(tab)[i] = src[i];
   }
   if (staged)
-    for (int i = tid; i < cd.count; i += WF_THREADS) pts[i] = a.points[cd.offset + i];
+    for (int i = tid; i < cd.count; i += FR_THREADS) pts[i] = a.points[cd.offset + i];
   // the channel: tap l from words (0,1) (l even) or (2,3) (l odd) of counter 0xFFFFFFF0 + l/2; one tap (1, 0) without it
   if (tid < WF_MAX_TAPS) {
     float2 hv = make_float2(0.f, 0.f);
@@ -157,7 +146,7 @@ __global__ __launch_bounds__(WF_THREADS) void frames_waveform_kernel(WfArgs a) {
   if (kind == 1) {
     // CPM: PHI[n'] = sum_{j <= n'} inc[j] mod 2^32, inc[j] = sum_i b[j/sps + i] * fpulse[q][j%sps][i].  Thread t owns [start, end).
     const uint32_t* ft = reinterpret_cast<const uint32_t*>(tab);
-    const int chunk = (nu + WF_THREADS - 1) / WF_THREADS;
+    const int chunk = (nu + FR_THREADS - 1) / FR_THREADS;
     const int start = min(tid * chunk, nu), end = min(start + chunk, nu);
     auto inc_at = [&](int m, int r) {
       uint32_t s = 0;
@@ -170,16 +159,7 @@ __global__ __launch_bounds__(WF_THREADS) void frames_waveform_kernel(WfArgs a) {
       s += inc_at(m, r);
       if (++r == sps) { r = 0; ++m; }
     }
-    uint32_t inc = s;
-#pragma unroll
-    for (int o = 1; o < IQ_WAVE; o <<= 1) {
-      const uint32_t t = __shfl_up(inc, o, IQ_WAVE);
-      if (lane >= o) inc += t;
-    }
-    if (lane == IQ_WAVE - 1) wsum[wave] = inc;
-    __syncthreads();
-    uint32_t run = inc - s;
-    for (int i = 0; i < wave; ++i) run += wsum[i];
+    uint32_t run = scan_exclusive(s, wsum, lane, wave);
     m = start / sps; r = start - m * sps;
     for (int n = start; n < end; ++n) {
       run += inc_at(m, r);
@@ -190,7 +170,7 @@ __global__ __launch_bounds__(WF_THREADS) void frames_waveform_kernel(WfArgs a) {
     }
   } else if (kind == 0) {
     const float2* gp = a.points + cd.offset;
-    for (int n = tid; n < nu; n += WF_THREADS) {
+    for (int n = tid; n < nu; n += FR_THREADS) {
       const int m = n / sps, r = n - m * sps;
       const float* pr = tab + r * span;
       const float2 a0 = staged ? pts[w[m]] : gp[w[m]];
@@ -205,16 +185,16 @@ __global__ __launch_bounds__(WF_THREADS) void frames_waveform_kernel(WfArgs a) {
   } else {
     // OQPSK: the I rail at n', the Q rail at n' + sps/2
     const int half = sps >> 1;
-    for (int n = tid; n < nu; n += WF_THREADS) {
+    for (int n = tid; n < nu; n += FR_THREADS) {
       const int m = n / sps, r = n - m * sps;
       const int m2 = (n + half) / sps, r2 = n + half - m2 * sps;
       const float* pr = tab + r * span;
       const float* pr2 = tab + r2 * span;
-      float ur = ((w[m] & 2) ? WF_RSQRT2 : -WF_RSQRT2) * pr[0];
-      float ui = ((w[m2] & 1) ? WF_RSQRT2 : -WF_RSQRT2) * pr2[0];
+      float ur = ((w[m] & 2) ? FR_RSQRT2 : -FR_RSQRT2) * pr[0];
+      float ui = ((w[m2] & 1) ? FR_RSQRT2 : -FR_RSQRT2) * pr2[0];
       for (int i = 1; i < span; ++i) {
-        ur = fmaf((w[m + i] & 2) ? WF_RSQRT2 : -WF_RSQRT2, pr[i], ur);
-        ui = fmaf((w[m2 + i] & 1) ? WF_RSQRT2 : -WF_RSQRT2, pr2[i], ui);
+        ur = fmaf((w[m + i] & 2) ? FR_RSQRT2 : -FR_RSQRT2, pr[i], ur);
+        ui = fmaf((w[m2 + i] & 1) ? FR_RSQRT2 : -FR_RSQRT2, pr2[i], ui);
       }
       fr[n] = make_float2(ur, ui);
     }
@@ -224,7 +204,7 @@ __global__ __launch_bounds__(WF_THREADS) void frames_waveform_kernel(WfArgs a) {
   // ---- channel, carrier phase, power.  Round k: n = 256 k + tid.
   float pw = 0.f, hp = 0.f;
   for (int l = 0; l < L; ++l) hp = fmaf(h[l].y, h[l].y, fmaf(h[l].x, h[l].x, hp));
-  for (int base = 0; base < len; base += WF_THREADS) {
+  for (int base = 0; base < len; base += FR_THREADS) {
     const int n = base + tid;
     float2 v = make_float2(0.f, 0.f);
     if (n < len) {
@@ -240,61 +220,23 @@ __global__ __launch_bounds__(WF_THREADS) void frames_waveform_kernel(WfArgs a) {
     }
     if (L > 1) __syncthreads();
     if (n < len) {
-      // synth.hip's `v.x * c0 - v.y * s0` and `v.x * s0 + v.y * c0` as the compiler contracts them there (one product rounded,
-      // the other fused), spelled out: here the same expression compiles to two products and an add, and the identity
-      // configuration would differ from iq_frames_synth in the last bit
-      const float xr = fmaf(v.x, c0, -__fmul_rn(v.y, s0)), yr = fmaf(v.x, s0, __fmul_rn(v.y, c0));
-      fr[n] = make_float2(xr, yr);
-      pw = fmaf(yr, yr, fmaf(xr, xr, pw));
+      const float2 r = rotate(v, c0, s0);
+      fr[n] = r;
+      pw = fmaf(r.y, r.y, fmaf(r.x, r.x, pw));
     }
   }
   if (L == 1 && (len & 1) && tid == 0) fr[len] = make_float2(0.f, 0.f);     // the second half of the last pair
-  pw = wave_sum(pw);
-  if (lane == 0) red[wave] = pw;
-  __syncthreads();
-
-  const float P = (((red[0] + red[1]) + red[2]) + red[3]) / (float)len;
-  const float rs = 1.f / sqrtf(P + 1e-12f);
-  float snr = nanf(""), sig = 0.f;
-  if (NOISE) {
-    snr = a.snrs_db[si];
-    sig = sqrtf(0.5f * powf(10.f, -snr / 10.f));
-  }
+  const float snr = NOISE ? a.snrs_db[si] : nanf("");
+  const FrameScale f = frame_scale(pw, red, len, lane, wave, NOISE, snr);
   if (tid == 0) {
     a.labels[fi] = cls;
     a.snr[fi] = snr;
     if (a.drawn) {
-      reinterpret_cast<float4*>(a.drawn)[2 * fi] = make_float4((float)cls, snr, WF_TWO_PI * turn, P);
+      reinterpret_cast<float4*>(a.drawn)[2 * fi] = make_float4((float)cls, snr, FR_TWO_PI * turn, f.P);
       reinterpret_cast<float4*>(a.drawn)[2 * fi + 1] = make_float4((float)q, hp, 0.f, 0.f);
     }
   }
-
-  // ---- two consecutive samples per thread: normalise, add the noise, one 16-byte store
-  float* dst = a.raw + fi * len * 2;
-  for (int p = tid; p < nq; p += WF_THREADS) {
-    float4 v = reinterpret_cast<const float4*>(fr)[p];
-    v.x *= rs; v.y *= rs; v.z *= rs; v.w *= rs;
-    if (NOISE) {
-      const u32x4 z = philox4x32(WF_NOISE_CTR + (uint32_t)p, flo, IQ_SITE_SYNTH, a.stream, k0, k1);
-      float g0, g1, g2, g3;
-      box_muller(z[0], z[1], g0, g1);
-      box_muller(z[2], z[3], g2, g3);
-      v.x = fmaf(sig, g0, v.x); v.y = fmaf(sig, g1, v.y);
-      v.z = fmaf(sig, g2, v.z); v.w = fmaf(sig, g3, v.w);
-    }
-    if (a.st4) {
-      reinterpret_cast<float4*>(dst)[p] = v;
-    } else {
-      reinterpret_cast<float2*>(dst)[2 * p] = make_float2(v.x, v.y);
-      if (2 * p + 1 < len) reinterpret_cast<float2*>(dst)[2 * p + 1] = make_float2(v.z, v.w);
-    }
-  }
-}
-
-template <bool NOISE>
-void launch(const WfArgs& a, int n_frames, size_t lds, hipStream_t st) {
-  if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)frames_waveform_kernel<NOISE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  frames_waveform_kernel<NOISE><<<n_frames, WF_THREADS, lds, st>>>(a);
+  store_frame(a.raw + fi * len * 2, fr, len, a.st4, tid, f, NOISE, WF_NOISE_CTR, flo, IQ_SITE_SYNTH, a.stream, k0, k1);
 }
 
 }  // namespace
@@ -303,8 +245,8 @@ extern "C" int iq_frames_waveform(float* raw, int64_t* labels, float* snr, float
                                   int n_frames, int len, const iq_waveform_t* par, iq_stream_t stream) {
   if (!raw || !labels || !snr || !par) return IQ_ERR_ARG;
   if (len <= 0) return IQ_ERR_ARG;
-  if (!par->classes || par->n_classes <= 0 || par->n_snrs < 0 || (par->n_snrs > 0 && !par->snrs_db)) return IQ_ERR_ARG;
-  if ((par->balanced & ~1) || (par->timing & ~1)) return IQ_ERR_ARG;
+  if (!synth_lists_ok(par->classes, par->n_classes, par->snrs_db, par->n_snrs, par->points, par->balanced)) return IQ_ERR_ARG;
+  if (par->timing & ~1) return IQ_ERR_ARG;
   if (par->sps < 1 || par->span < 1 || par->n_phase < 1 || par->n_taps < 1) return IQ_ERR_ARG;
   if (((uintptr_t)raw & 7) || ((uintptr_t)labels & 7) || ((uintptr_t)snr & 3) || ((uintptr_t)drawn & 15) ||
       ((uintptr_t)symbols & 3) || ((uintptr_t)taps & 7) || ((uintptr_t)par->points & 7) || ((uintptr_t)par->pulse & 3) ||
@@ -314,20 +256,15 @@ extern "C" int iq_frames_waveform(float* raw, int64_t* labels, float* snr, float
   int npts = 0;
   for (int i = 0; i < nc; ++i) {
     const iq_synth_class_t& c = par->classes[i];
-    if (c.kind < 0 || c.kind > 2) return IQ_ERR_ARG;
-    if (c.kind == 0 && (c.count <= 0 || c.offset < 0 || !par->points)) return IQ_ERR_ARG;
     if (c.kind == 1 ? !par->fpulse : !par->pulse) return IQ_ERR_ARG;
     if (c.kind == 0 && c.count <= WF_POINTS_LDS && c.count > npts) npts = c.count;
   }
-  const int ns = par->n_snrs < IQ_SYNTH_MAX_SNRS ? par->n_snrs : IQ_SYNTH_MAX_SNRS;
-  for (int i = 0; i < ns; ++i)
-    if (!(fabsf(par->snrs_db[i]) < INFINITY)) return IQ_ERR_ARG;
-  if (!(fabsf(par->los) < INFINITY)) return IQ_ERR_ARG;
+  if (!is_finite(par->los)) return IQ_ERR_ARG;
   for (int l = 0; l < par->n_taps && l < WF_MAX_TAPS; ++l)
     if (!(par->tap_sigma[l] >= 0.f && par->tap_sigma[l] < INFINITY)) return IQ_ERR_ARG;
   if (par->sps > WF_MAX_SPS || par->span > WF_MAX_SPAN || par->n_phase > WF_MAX_PHASE || par->n_taps > WF_MAX_TAPS)
     return IQ_ERR_UNSUPPORTED;
-  if ((size_t)len * 8 > 64 * 1024) return IQ_ERR_UNSUPPORTED;
+  if (!frame_fits(len)) return IQ_ERR_UNSUPPORTED;
   if (par->n_classes > IQ_SYNTH_MAX_CLASSES || par->n_snrs > IQ_SYNTH_MAX_SNRS) return IQ_ERR_UNSUPPORTED;
   if (n_frames <= 0) return IQ_OK;
   hipStream_t st = (hipStream_t)stream;
@@ -342,18 +279,16 @@ extern "C" int iq_frames_waveform(float* raw, int64_t* labels, float* snr, float
   a.ns = (nu + par->sps) / par->sps + par->span;
   a.npts = (npts + 1) & ~1;                     // the taps behind it stay 16-byte aligned
   a.seed = par->seed; a.frame_base = par->frame_base; a.stream = par->stream;
-  a.st4 = (len % 2 == 0 && ((uintptr_t)raw & 15) == 0) ? 1 : 0;
+  a.st4 = frame_vec4(raw, len);
   a.los = par->los;
   for (int l = 0; l < WF_MAX_TAPS; ++l) a.tap_sigma[l] = l < par->n_taps ? par->tap_sigma[l] : 0.f;
-  for (int i = 0; i < IQ_SYNTH_MAX_CLASSES; ++i) a.classes[i] = i < par->n_classes ? par->classes[i] : iq_synth_class_t{1, 0, 0};
-  for (int i = 0; i < IQ_SYNTH_MAX_SNRS; ++i) a.snrs_db[i] = i < par->n_snrs ? par->snrs_db[i] : 0.f;
+  pack_synth_lists(a.classes, a.snrs_db, par->classes, par->n_classes, par->snrs_db, par->n_snrs);
   const bool noise = par->n_snrs > 0;
   const int nt = par->sps * par->span;
   const size_t lds = (size_t)((nu + 1) / 2) * 16 + (size_t)((a.ns + 3) / 4) * 16 + (size_t)((nt + 3) & ~3) * 4 +
-                     (size_t)a.npts * sizeof(float2) + WF_MAX_TAPS * sizeof(float2) + WF_WAVES * (sizeof(float) + sizeof(uint32_t));
+                     (size_t)a.npts * sizeof(float2) + WF_MAX_TAPS * sizeof(float2) + FR_WAVES * (sizeof(float) + sizeof(uint32_t));
   const double bytes = (double)n_frames * ((double)len * 8 + 12 + (drawn ? 32 : 0) + (symbols ? (double)a.ns * 4 : 0) + (taps ? 64 : 0));
   IQ_PROF_K(bytes, 0.0, "frames_waveform_kernel<%s>", noise ? "true" : "false");
-  if (noise) launch<true>(a, n_frames, lds, st);
-  else launch<false>(a, n_frames, lds, st);
+  launch_frames(noise ? frames_waveform_kernel<true> : frames_waveform_kernel<false>, n_frames, lds, st, a);
   return iq_launch_status();
 }

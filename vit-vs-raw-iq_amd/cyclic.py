@@ -35,7 +35,7 @@ import torch
 
 from . import _native as N
 from .impairments import _index, _number
-from .spectrogram import FFT_STEP, MAX_FFT, MAX_LENGTH, MIN_FFT, WINDOWS, _host, _twiddles, _window
+from .spectrogram import FFT_STEP, MAX_FFT, MAX_LENGTH, MIN_FFT, WINDOWS, _fit, _host, _on_device, _twiddles, _window
 
 KINDS = ("scf", "conj", "both")
 MODES = ("power", "log", "coherence")
@@ -101,23 +101,13 @@ class CyclicSpectrum:
                         mode=MODES.index(self.mode), inv_norm=self.inv_norm, floor=self.floor, scale=self.scale,
                         shift=self.shift)
 
-    @staticmethod
-    def _on(cache, host, device):
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        t = cache.get(device)
-        if t is None:
-            t = cache[device] = torch.from_numpy(host).to(device)
-        return t
-
     def table_on(self, device):
         """The fp32 (c, s) table on `device` (uploaded once per device)."""
-        return self._on(self._tables, self.table, device)
+        return _on_device(self._tables, self.table, device)
 
     def rot_on(self, device):
         """The fp32 rot table on `device` (uploaded once per device)."""
-        return self._on(self._rots, self.rot, device)
+        return _on_device(self._rots, self.rot, device)
 
     def _check(self, x, what="x"):
         if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.shape[1] != 2 or x.shape[2] != self.length:
@@ -147,15 +137,7 @@ class CyclicSpectrum:
         """Set scale and shift so that the images of `x_subset` (device (B, 2, len)) have zero mean and unit standard deviation
         (unbiased, floored at 1e-8): one call with scale 1 and shift 0, then a device mean / std.  One host synchronisation.
         -> self."""
-        self._check(x_subset, "x_subset")
-        if x_subset.shape[0] < 1:
-            raise ValueError("x_subset is empty")
-        self.scale, self.shift = 1.0, 0.0
-        with torch.no_grad():
-            std, mean = torch.std_mean(self(x_subset))
-        mean, std = float(mean), max(float(std), 1e-8)
-        self.scale, self.shift = _number(1.0 / std, "scale"), _number(-mean / std, "shift")
-        return self
+        return _fit(self, x_subset)
 
     def __repr__(self):
         return (f"CyclicSpectrum(n_fft={self.n_fft}, length={self.length}, hop={self.hop}, pad={self.pad}, "

@@ -50,6 +50,30 @@ def _twiddles(n_fft, w):
     return w[:, None] * np.cos(ang), w[:, None] * np.sin(ang)
 
 
+def _on_device(cache, host, device):
+    """The numpy table `host` as a tensor on `device`, uploaded once per device (`cache`: {device: tensor})."""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    t = cache.get(device)
+    if t is None:
+        t = cache[device] = torch.from_numpy(host).to(device)
+    return t
+
+
+def _fit(front, x_subset):
+    """fit() of a front end (a Spectrogram or a CyclicSpectrum): one call with scale 1 and shift 0, then a device mean / std."""
+    front._check(x_subset, "x_subset")
+    if x_subset.shape[0] < 1:
+        raise ValueError("x_subset is empty")
+    front.scale, front.shift = 1.0, 0.0
+    with torch.no_grad():
+        std, mean = torch.std_mean(front(x_subset))
+    mean, std = float(mean), max(float(std), 1e-8)
+    front.scale, front.shift = _number(1.0 / std, "scale"), _number(-mean / std, "shift")
+    return front
+
+
 class Spectrogram:
     """The geometry and scaling of one front end.  Defaults: hop = max(1, length // width), pad = max(0, ceil(((width-1)*hop +
     n_fft - length) / 2)) (the windows are centred on the frame), inv_norm = 1 / sum w^2.  Arguments are checked here, before
@@ -99,13 +123,7 @@ class Spectrogram:
 
     def table_on(self, device):
         """The fp32 table on `device` (uploaded once per device)."""
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        t = self._tables.get(device)
-        if t is None:
-            t = self._tables[device] = torch.from_numpy(self.table).to(device)
-        return t
+        return _on_device(self._tables, self.table, device)
 
     def _check(self, x, what="x"):
         if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.shape[1] != 2 or x.shape[2] != self.length:
@@ -125,16 +143,7 @@ class Spectrogram:
         """Set scale and shift so that the images of `x_subset` (device (B, 2, len)) have zero mean and unit standard deviation
         (unbiased, floored at 1e-8): one call with scale 1 and shift 0, then a device mean / std.  One host synchronisation.
         -> self."""
-        self._check(x_subset, "x_subset")
-        if x_subset.shape[0] < 1:
-            raise ValueError("x_subset is empty")
-        self.scale, self.shift = 1.0, 0.0
-        with torch.no_grad():
-            img = self(x_subset)
-            std, mean = torch.std_mean(img)
-        mean, std = float(mean), max(float(std), 1e-8)
-        self.scale, self.shift = _number(1.0 / std, "scale"), _number(-mean / std, "shift")
-        return self
+        return _fit(self, x_subset)
 
     def __repr__(self):
         return (f"Spectrogram(n_fft={self.n_fft}, width={self.width}, length={self.length}, hop={self.hop}, pad={self.pad}, "

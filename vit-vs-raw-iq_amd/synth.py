@@ -61,6 +61,10 @@ class FrameSynth:
     rounded to the fp32 table the kernel reads.  snrs_db: the SNR values in dB, None or () for noiseless frames.  Arguments are
     checked here, before any device work; the table goes to `device` at the first generate()."""
 
+    _drawn_columns = 4
+    _no_cpu = ("FrameSynth.generate runs on the MI355X only: there is no CPU fallback "
+               "(synth_reference is the host definition used by the tests)")
+
     def __init__(self, classes=D.CLASSES, snrs_db=D.SNRS_DB, length: int = 1024, seed: int = 0, balanced: bool = True,
                  device="cuda"):
         items = list(classes.items()) if isinstance(classes, dict) else [(c, None) for c in classes]
@@ -95,6 +99,7 @@ class FrameSynth:
             raise ValueError(f"at most {MAX_SNRS} SNR values, got {len(snrs)}")
         self.snrs_db = tuple(snrs)
         self.length = _index(length, "length", 1, MAX_LENGTH)
+        self.n_symbols = self.length                 # columns of `symbols`
         self.seed = _index(seed, "seed", 0, 2 ** 64 - 1)
         self.balanced = _flag(balanced, "balanced")
         self.device = torch.device(device)
@@ -116,30 +121,36 @@ class FrameSynth:
         """Frames [frame_base, frame_base + n) of `stream` -> (raw (n, len, 2) fp32, y (n,) int64, z (n,) fp32 SNR in dB, NaN
         without noise), all on the device; then, if asked for, drawn (n, 4) fp32 = {class, snr_db, theta, mean |s|^2 before
         the normalisation} and symbols (n, len) int32 (constellation index; GMSK: phase in units of pi/8; OQPSK: 2 I + Q)."""
+        return self._generate(n, frame_base, stream, return_drawn, return_symbols)
+
+    def _generate(self, n, frame_base, stream, return_drawn, return_symbols, **extra):
+        """generate() of this class and of its subclasses: the checks, the outputs every generator has, _launch, the tuple."""
         n = _index(n, "n", 0, 2 ** 31 - 1)
         par = self.struct(frame_base, stream)
         if self.device.type != "cuda":
-            raise N.IqError("FrameSynth.generate runs on the MI355X only: there is no CPU fallback "
-                            "(synth_reference is the host definition used by the tests)")
+            raise N.IqError(self._no_cpu)
         d = self.device
-        if self._points_dev is None:
-            self._points_dev = torch.from_numpy(self.points if len(self.points) else np.zeros((1, 2), np.float32)).to(d)
-        par.points = self._points_dev.data_ptr()
         raw = torch.empty(n, self.length, 2, dtype=torch.float32, device=d)
         y = torch.empty(n, dtype=torch.int64, device=d)
         z = torch.empty(n, dtype=torch.float32, device=d)
-        drawn = torch.empty(n, 4, dtype=torch.float32, device=d) if return_drawn else None
-        symbols = torch.empty(n, self.length, dtype=torch.int32, device=d) if return_symbols else None
+        drawn = torch.empty(n, self._drawn_columns, dtype=torch.float32, device=d) if return_drawn else None
+        symbols = torch.empty(n, self.n_symbols, dtype=torch.int32, device=d) if return_symbols else None
+        more = self._launch(par, n, raw, y, z, drawn, symbols, **extra)
+        return (raw, y, z) + tuple(t for t in (drawn, symbols) + more if t is not None)
+
+    def _points_ptr(self):
+        if self._points_dev is None:
+            self._points_dev = torch.from_numpy(self.points if len(self.points) else np.zeros((1, 2), np.float32)).to(self.device)
+        return self._points_dev.data_ptr()
+
+    def _launch(self, par, n, raw, y, z, drawn, symbols):
+        """The tables to the device at the first call, then the kernel (n > 0) -> the further outputs of a subclass."""
+        par.points = self._points_ptr()
         if n > 0:
             N.check(N.lib().iq_frames_synth(raw.data_ptr(), y.data_ptr(), z.data_ptr(), N.ptr(drawn), N.ptr(symbols), n,
-                                            self.length, C.byref(par), torch.cuda.current_stream(d).cuda_stream),
+                                            self.length, C.byref(par), torch.cuda.current_stream(self.device).cuda_stream),
                     "iq_frames_synth")
-        out = (raw, y, z)
-        if return_drawn:
-            out += (drawn,)
-        if return_symbols:
-            out += (symbols,)
-        return out
+        return ()
 
     def stats(self, n_subset: int = 5000, stream: int = 0):
         """{'i_mean','i_std','q_mean','q_std'} as data.normalization_stats computes them (fp32 values, unbiased std floored at

@@ -126,6 +126,10 @@ class ShapedSynth(FrameSynth):
     scatter sqrt(p_0 / (2 (K + 1))) per component), taps l >= 1 Rayleigh with sqrt(p_l / 2) per component, drawn per frame.
     pulse= / fpulse=: tables of one's own, (n_phase, sps, span).  Arguments are checked here, before any device work."""
 
+    _drawn_columns = 8
+    _no_cpu = ("ShapedSynth.generate runs on the MI355X only: there is no CPU fallback "
+               "(waveform_reference is the host definition used by the tests)")
+
     def __init__(self, classes=D.CLASSES, snrs_db=D.SNRS_DB, length: int = 1024, seed: int = 0, balanced: bool = True,
                  device="cuda", sps: int = 8, span: int = 8, alpha: float = 0.35, bt: float = 0.3, n_phase: int = 32,
                  timing: bool = True, taps: int = 1, rice_k_db: float = 6.0, decay: float = 0.5, pulse=None, fpulse=None):
@@ -164,35 +168,20 @@ class ShapedSynth(FrameSynth):
         without noise), all on the device; then, if asked for, drawn (n, 8) fp32 = {class, snr_db, theta, mean |v|^2 before the
         normalisation, timing phase q, sum |h_l|^2, 0, 0}, symbols (n, n_symbols) int32 (constellation index; GMSK: the bit;
         OQPSK: 2 I + Q) and taps (n, 8, 2) fp32 (re, im), zeros beyond `taps`."""
-        n = _index(n, "n", 0, 2 ** 31 - 1)
-        par = self.struct(frame_base, stream)
-        if self.device.type != "cuda":
-            raise N.IqError("ShapedSynth.generate runs on the MI355X only: there is no CPU fallback "
-                            "(waveform_reference is the host definition used by the tests)")
+        return self._generate(n, frame_base, stream, return_drawn, return_symbols, return_taps=return_taps)
+
+    def _launch(self, par, n, raw, y, z, drawn, symbols, return_taps=False):
         d = self.device
-        if self._points_dev is None:
-            self._points_dev = torch.from_numpy(self.points if len(self.points) else np.zeros((1, 2), np.float32)).to(d)
+        if self._pulse_dev is None:
             self._pulse_dev = torch.from_numpy(self.pulse).to(d)
             self._fpulse_dev = torch.from_numpy(self.fpulse).to(d)
-        par.points, par.pulse, par.fpulse = self._points_dev.data_ptr(), self._pulse_dev.data_ptr(), self._fpulse_dev.data_ptr()
-        raw = torch.empty(n, self.length, 2, dtype=torch.float32, device=d)
-        y = torch.empty(n, dtype=torch.int64, device=d)
-        z = torch.empty(n, dtype=torch.float32, device=d)
-        drawn = torch.empty(n, 8, dtype=torch.float32, device=d) if return_drawn else None
-        symbols = torch.empty(n, self.n_symbols, dtype=torch.int32, device=d) if return_symbols else None
+        par.points, par.pulse, par.fpulse = self._points_ptr(), self._pulse_dev.data_ptr(), self._fpulse_dev.data_ptr()
         taps = torch.empty(n, 8, 2, dtype=torch.float32, device=d) if return_taps else None
         if n > 0:
             N.check(N.lib().iq_frames_waveform(raw.data_ptr(), y.data_ptr(), z.data_ptr(), N.ptr(drawn), N.ptr(symbols),
                                                N.ptr(taps), n, self.length, C.byref(par),
                                                torch.cuda.current_stream(d).cuda_stream), "iq_frames_waveform")
-        out = (raw, y, z)
-        if return_drawn:
-            out += (drawn,)
-        if return_symbols:
-            out += (symbols,)
-        if return_taps:
-            out += (taps,)
-        return out
+        return (taps,)
 
     def __repr__(self):
         return (f"ShapedSynth(classes={self.class_names!r}, snrs_db={self.snrs_db!r}, length={self.length}, seed={self.seed}, "
