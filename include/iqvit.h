@@ -215,6 +215,48 @@ int iq_gemm_bf16_wgrad_grouped(const iq_wgrad_problem_t* probs, int nprob, int M
                                int accumulate, int max_workgroups, const iq_reduce_seg_t* extra, int nextra,
                                iq_stream_t stream);
 
+/* The slab reduce of a group as a job that can run later on the same stream: the segments (weights, biases, extra), in
+ * the block order of the stand-alone launch.  Filled by iq_gemm_bf16_wgrad_grouped_deferred; callers treat it as opaque.
+ * seg[i] owns virtual blocks [blk0, next blk0): 256 threads each, "wide" = 64 float4 columns x 4 row slices, "tall" = 16
+ * columns x 16 slices (csrc/wgrad_reduce.h). */
+#define IQ_REDUCE_JOB_SEGS 12
+typedef struct iq_reduce_job_seg {
+  const float* partials; /* [rows][stride] */
+  float* out;            /* [n] */
+  int64_t n;
+  int64_t stride;        /* floats */
+  int rows;
+  int blk0;
+  int tall;
+} iq_reduce_job_seg_t;
+typedef struct iq_reduce_job {
+  iq_reduce_job_seg_t seg[IQ_REDUCE_JOB_SEGS];
+  int nseg;
+  int nblk;       /* virtual blocks in all; 0 = nothing to do */
+  int accumulate;
+} iq_reduce_job_t;
+/* iq_gemm_bf16_wgrad_grouped without its last launch: the partial-tile kernel runs, the slab reduce (+ the extra
+ * segments) comes back in *job.  The job reads `ws`, the extra segments' partials and (accumulate) the outputs, so it must
+ * run on the same stream before anything overwrites them: stand-alone with iq_reduce_job_run, or inside a later launch
+ * that has room for it (iq_gemm_bf16_lnbwd_ride).  A group that runs one problem at a time through the shared slab area
+ * reduces those problems at once, as iq_gemm_bf16_wgrad_grouped does, and only the extra segments are left in the job.
+ * iq_gemm_bf16_wgrad_grouped == deferred + run: the same kernels, the same bits. */
+int iq_gemm_bf16_wgrad_grouped_deferred(const iq_wgrad_problem_t* probs, int nprob, int M, float* ws, size_t ws_bytes,
+                                        int accumulate, int max_workgroups, const iq_reduce_seg_t* extra, int nextra,
+                                        iq_reduce_job_t* job, iq_stream_t stream);
+int iq_reduce_job_run(const iq_reduce_job_t* job, iq_stream_t stream);
+/* iq_gemm_bf16_lnbwd with a reduce job riding in the launch: where the row tiles leave workgroup slots of the GPU free
+ * (resident workgroups per CU x CUs - tiles, at least 64), that many extra workgroups behind the tiles sum the job's
+ * virtual blocks, with the arithmetic of the stand-alone launch bit for bit, and no launch is spent on the reduce.
+ * Otherwise the job runs stand-alone first, then the plain launch.  Nothing the tiles write may be read by the job and
+ * vice versa (the model alternates the norm2 partial rows between two buffers for this).  job NULL or empty = iq_gemm_bf16_lnbwd.
+ * iq_gemm_lnbwd_ride_workgroups: the reduce workgroups such a call appends for a job of `job_blocks` virtual blocks on the
+ * current device (asks the runtime for the kernel's occupancy); 0 = the call falls back to the stand-alone reduce. */
+int iq_gemm_lnbwd_ride_workgroups(int M, int D, int K, int job_blocks);
+int iq_gemm_bf16_lnbwd_ride(const void* A, int lda, const void* Wt, int ldw, const void* residual, int ldr, const void* z,
+                            const float* mean, const float* rstd, const float* gamma, const iq_dropout_t* drop, void* dz,
+                            void* dy, float* partial, int M, int D, int K, const iq_reduce_job_t* job, iq_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------
  * Scaled-dot-product attention core, softmax(Q K^T / sqrt(dh)) V per (frame, head), no mask,
  * no dropout.  Replaces ScaleDotProductAttention.forward

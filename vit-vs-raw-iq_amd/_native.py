@@ -81,6 +81,15 @@ class ReduceSeg(C.Structure):
                 ("n", C.c_int64)]
 
 
+class ReduceJobSeg(C.Structure):
+    _fields_ = [("partials", C.c_void_p), ("out", C.c_void_p), ("n", C.c_int64), ("stride", C.c_int64), ("rows", C.c_int),
+                ("blk0", C.c_int), ("tall", C.c_int)]
+
+
+class ReduceJob(C.Structure):      # filled by iq_gemm_bf16_wgrad_grouped_deferred, opaque to callers
+    _fields_ = [("seg", ReduceJobSeg * 12), ("nseg", C.c_int), ("nblk", C.c_int), ("accumulate", C.c_int)]
+
+
 class ModelCfg(C.Structure):
     _fields_ = [("kind", C.c_int), ("in_channels", C.c_int), ("img_h", C.c_int), ("img_w", C.c_int),
                 ("patch", C.c_int), ("seq_length", C.c_int), ("conv_k", C.c_int), ("use_cls", C.c_int),
@@ -119,6 +128,11 @@ SIGNATURES = {
     "iq_gemm_bf16_wgrad": (_I, [_P, _I, _P, _I, _P, _P, _I, _I, _I, _P, _Z, _I, _P]),
     "iq_wgrad_grouped_ws_bytes": (_Z, [_P, _I, _I, _I]),
     "iq_gemm_bf16_wgrad_grouped": (_I, [_P, _I, _I, _P, _Z, _I, _I, _P, _I, _P]),
+    "iq_gemm_bf16_wgrad_grouped_deferred": (_I, [_P, _I, _I, _P, _Z, _I, _I, _P, _I, C.POINTER(ReduceJob), _P]),
+    "iq_reduce_job_run": (_I, [C.POINTER(ReduceJob), _P]),
+    "iq_gemm_bf16_lnbwd_ride": (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _P, _P, C.POINTER(Dropout), _P, _P, _P, _I, _I, _I,
+                                     C.POINTER(ReduceJob), _P]),
+    "iq_gemm_lnbwd_ride_workgroups": (_I, [_I, _I, _I, _I]),
     "iq_attn_supported": (_I, [_I, _I]),
     "iq_attn_fwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "iq_attn_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),

@@ -20,16 +20,33 @@
 // LayerNorm in the MFMA register layout instead (rows spread over two waves, 96 accumulators + 48 Z registers + 96
 // recomputed xhat live at once) spilled 26-98 registers whatever was tried.  The Z rows are requested behind the last
 // ring stage (counted vmcnt), mean / rstd / gamma wait in LDS from the start of the kernel.
+//
+// iq_gemm_bf16_lnbwd_ride: the same launch with workgroups behind the row tiles that run the slab reduce of the weight
+// gradients launched before it (wgrad_reduce.h), where the tiles leave slots of the GPU free -- cfg B: 394 tiles of 128
+// rows on 2 x 256 slots.  The reduce then costs no launch of its own.
 
 #include "common.h"
 #include "gemm_common.h"
 #include "gemm_ring.h"
 #include "iqvit.h"
 #include "prof.h"
+#include "wgrad_reduce.h"
 
 namespace {
 
 constexpr int LB_THREADS = 256;
+static_assert(LB_THREADS == RED_THREADS, "a reduce-role workgroup is a virtual block of the slab reduce");
+
+// The reduce role (iq_gemm_bf16_lnbwd_ride): workgroups behind the row tiles sum the slabs of the weight-gradient launch
+// before this one instead of multiplying.  They dispatch after the tiles (higher block indices) into the slots the tiles
+// leave free, read nothing a tile writes and signal nobody.  A workgroup walks its virtual blocks one at a time with
+// RIDE_ROWS slab rows of a thread's column requested before the first sum.  Measured on cfg B (<128, 192>, mean time of
+// the launch; 38.0 us without a job, the stand-alone reduce 12.5): virtual blocks at a time x rows --
+//   4 x 8: 48.4   2 x 8: 47.2   1 x 8: 45.6   1 x 4: 58.3   1 x 2: 74.5 us  (profiles/wgrad_reduce_ride.txt)
+// Deeper bursts finish the role early but take the memory system from the tiles' main loop; with fewer than 8 rows in
+// flight the role outlasts the tiles.  32 registers of loads: within every instance's own allocation (the narrowest
+// takes 100), which matters because a kernel is allocated what its hungriest path needs.
+constexpr int RIDE_ROWS = 8;
 
 struct LnBwdParams {
   const bf16* A; const bf16* B; const bf16* residual;     // [M,K], [D,K], [M,D]
@@ -41,7 +58,7 @@ struct LnBwdParams {
 };
 
 template <int BMT, int BN>
-__global__ __launch_bounds__(LB_THREADS, 2) void gemm_lnbwd_kernel(const LnBwdParams p) {
+__global__ __launch_bounds__(LB_THREADS, 2) void gemm_lnbwd_kernel(const LnBwdParams p, const RedGroup job) {
   using Ring = RingShape<BMT, BN>;
   constexpr int BK2 = Ring::BK2, NS = Ring::NS, STAGE_BYTES = Ring::STAGE_BYTES, WN = Ring::WN, NT = Ring::NT, NP = NT / 2, MT = Ring::MT;
   constexpr int A_LD = Ring::A_LD, B_LD = Ring::B_LD, PER_STAGE = Ring::PER_STAGE, NRS = Ring::NRS;
@@ -49,6 +66,14 @@ __global__ __launch_bounds__(LB_THREADS, 2) void gemm_lnbwd_kernel(const LnBwdPa
   constexpr int N = BN;
   static_assert(NRS >= 2, "tile shape");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  static_assert(RED_THREADS * 16 <= NS * STAGE_BYTES, "the reduce role's LDS fits in the ring");
+  {
+    const int tiles = (p.M + BMT - 1) / BMT;
+    if ((int)blockIdx.x >= tiles) {                       // workgroup-uniform; only iq_gemm_bf16_lnbwd_ride launches such blocks
+      red_walk<RIDE_ROWS>(job, (int)blockIdx.x - tiles, (int)gridDim.x - tiles, reinterpret_cast<f32x4*>(smem));
+      return;
+    }
+  }
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
@@ -309,11 +334,44 @@ __global__ __launch_bounds__(LB_THREADS, 2) void gemm_lnbwd_kernel(const LnBwdPa
 }
 
 template <int BMT, int BN>
-int launch(const LnBwdParams& p, hipStream_t st) {
-  const size_t lds = RingShape<BMT, BN>::BYTES + (2 * BMT + BN) * sizeof(float);   // ring + mean | rstd | gamma
+constexpr size_t lnbwd_lds() { return RingShape<BMT, BN>::BYTES + (2 * BMT + BN) * sizeof(float); }   // ring + mean | rstd | gamma
+
+// Workgroups of this instance the GPU holds at once (resident per CU x CUs), asked of the runtime once; 0 = unknown.
+template <int BMT, int BN>
+int lnbwd_slots() {
+  static const int slots = [] {
+    auto k = gemm_lnbwd_kernel<BMT, BN>;
+    const size_t lds = lnbwd_lds<BMT, BN>();
+    if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    int dev = 0, cus = 0, per_cu = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, LB_THREADS, lds) != hipSuccess) {
+      (void)hipGetLastError();
+      return 0;
+    }
+    return per_cu * cus;
+  }();
+  return slots;
+}
+
+// A job rides only into a real hole: fewer free slots than this and each reduce workgroup walks so many virtual blocks
+// one after the other that the launch would end later than the reduce it saves (cfg B: 1,750 blocks on 118 workgroups =
+// 15 each, and the role already ends about when the tiles do; a quarter of the CUs' worth of slots is the least taken).
+constexpr int RIDE_MIN_WGS = 64;
+template <int BMT, int BN>
+int lnbwd_ride_wgs(int M, int nblk) {
+  const int tiles = (M + BMT - 1) / BMT, spare = lnbwd_slots<BMT, BN>() - tiles;
+  if (nblk <= 0 || spare < RIDE_MIN_WGS) return 0;
+  return spare < nblk ? spare : nblk;
+}
+
+// ride_wgs reduce-role workgroups behind the row tiles (0 and an empty job: the plain launch)
+template <int BMT, int BN>
+int launch(const LnBwdParams& p, const RedGroup& job, int ride_wgs, hipStream_t st) {
+  const size_t lds = lnbwd_lds<BMT, BN>();
   auto k = gemm_lnbwd_kernel<BMT, BN>;
   if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  k<<<(p.M + BMT - 1) / BMT, LB_THREADS, lds, st>>>(p);
+  k<<<(p.M + BMT - 1) / BMT + ride_wgs, LB_THREADS, lds, st>>>(p, job);
   return iq_launch_status();
 }
 
@@ -331,11 +389,14 @@ extern "C" int iq_gemm_lnbwd_partial_rows(int M) {
   return (M + r - 1) / r;
 }
 
-extern "C" int iq_gemm_bf16_lnbwd(const void* A, int lda, const void* Wt, int ldw, const void* residual, int ldr,
-                                  const void* z, const float* mean, const float* rstd, const float* gamma,
-                                  const iq_dropout_t* drop, void* dz, void* dy, float* partial, int M, int D, int K,
-                                  iq_stream_t stream) {
-  if (M <= 0) return IQ_OK;
+extern "C" int iq_gemm_bf16_lnbwd_ride(const void* A, int lda, const void* Wt, int ldw, const void* residual, int ldr,
+                                       const void* z, const float* mean, const float* rstd, const float* gamma,
+                                       const iq_dropout_t* drop, void* dz, void* dy, float* partial, int M, int D, int K,
+                                       const iq_reduce_job_t* job, iq_stream_t stream) {
+  const bool have_job = job && job->nblk > 0;
+  if (have_job && (job->nseg <= 0 || job->nseg > IQ_REDUCE_JOB_SEGS)) return IQ_ERR_ARG;
+  // (an argument error below leaves the job to the caller; an empty launch does not: the job still has to run)
+  if (M <= 0) return have_job ? iq_reduce_job_run(job, stream) : IQ_OK;
   if (!A || !Wt || !residual || !z || !mean || !rstd || !gamma || !dz || !partial) return IQ_ERR_ARG;
   if (!iq_gemm_lnbwd_supported(D, K) || (lda % 8) || (ldw % 8) || (ldr % 8)) return IQ_ERR_UNSUPPORTED;
   if (((uintptr_t)A | (uintptr_t)Wt | (uintptr_t)residual | (uintptr_t)z | (uintptr_t)dz | (uintptr_t)dy | (uintptr_t)gamma) % 16)
@@ -347,10 +408,36 @@ extern "C" int iq_gemm_bf16_lnbwd(const void* A, int lda, const void* Wt, int ld
   p.dZ = (bf16*)dz; p.dY = (bf16*)dy; p.partial = partial;
   if (!dropout_unpack(drop, &p.drop_on, &p.rng, &p.thresh, &p.dscale) || (p.drop_on && !dy)) return IQ_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
+  const bool b64 = lnbwd_block_rows(M) == 64;
+  RedGroup none = {};
+  int wgs = 0;
+  if (have_job) {
+    const int nblk = job->nblk;
+    wgs = b64 ? (D == 192 ? lnbwd_ride_wgs<64, 192>(M, nblk) : lnbwd_ride_wgs<64, 128>(M, nblk))
+              : (D == 192 ? lnbwd_ride_wgs<128, 192>(M, nblk) : lnbwd_ride_wgs<128, 128>(M, nblk));
+    if (wgs == 0) {                            // no hole behind the tiles: the stand-alone reduce, then the plain launch
+      const int rc = iq_reduce_job_run(job, stream);
+      if (rc != IQ_OK) return rc;
+    }
+  }
+  const RedGroup& rj = wgs > 0 ? *job : none;
   IQ_PROF(IQ_FAM_GEMM_NT, st);
-  // A + Wt + residual + Z read, dZ (+ dY) written
+  // A + Wt + residual + Z read, dZ (+ dY) written (a riding job's slab traffic is not algorithmic, as in wgrad_reduce_kernel's record)
   IQ_PROF_K(2.0 * ((double)M * K + (double)D * K + (double)M * D * (3 + (p.drop_on ? 1 : 0))) + 8.0 * M, 2.0 * (double)M * D * K,
             "gemm_lnbwd_kernel<%d, %d>", lnbwd_block_rows(M), D);
-  if (lnbwd_block_rows(M) == 64) return D == 192 ? launch<64, 192>(p, st) : launch<64, 128>(p, st);
-  return D == 192 ? launch<128, 192>(p, st) : launch<128, 128>(p, st);
+  if (b64) return D == 192 ? launch<64, 192>(p, rj, wgs, st) : launch<64, 128>(p, rj, wgs, st);
+  return D == 192 ? launch<128, 192>(p, rj, wgs, st) : launch<128, 128>(p, rj, wgs, st);
+}
+
+extern "C" int iq_gemm_lnbwd_ride_workgroups(int M, int D, int K, int job_blocks) {
+  if (M <= 0 || !iq_gemm_lnbwd_supported(D, K)) return 0;
+  if (lnbwd_block_rows(M) == 64) return D == 192 ? lnbwd_ride_wgs<64, 192>(M, job_blocks) : lnbwd_ride_wgs<64, 128>(M, job_blocks);
+  return D == 192 ? lnbwd_ride_wgs<128, 192>(M, job_blocks) : lnbwd_ride_wgs<128, 128>(M, job_blocks);
+}
+
+extern "C" int iq_gemm_bf16_lnbwd(const void* A, int lda, const void* Wt, int ldw, const void* residual, int ldr,
+                                  const void* z, const float* mean, const float* rstd, const float* gamma,
+                                  const iq_dropout_t* drop, void* dz, void* dy, float* partial, int M, int D, int K,
+                                  iq_stream_t stream) {
+  return iq_gemm_bf16_lnbwd_ride(A, lda, Wt, ldw, residual, ldr, z, mean, rstd, gamma, drop, dz, dy, partial, M, D, K, nullptr, stream);
 }

@@ -20,6 +20,7 @@
 #include "prof.h"
 
 #include "gemm_wgrad_big.h"
+#include "wgrad_reduce.h"
 
 namespace {
 
@@ -397,51 +398,12 @@ __global__ __launch_bounds__(PW_THREADS, 2) void wgrad_pw_kernel(const PwGroup g
   else pw_body<64, 64>(g, p, tile, split, smem);
 }
 
-// out[i] (+)= sum_s slab[s][i] for up to 2*PW_MAXP segments (weights and biases of a group) in ONE launch.
-// Block = 64 float4 columns x 4 split slices (coalesced 1 KiB rows, 4x the loads in flight of a one-thread-per-column
-// loop), slices combined through LDS in fixed order: bit-reproducible.
-constexpr int RED_MAXX = 4;   // extra (LayerNorm partial) segments
-struct RedSeg { const float* slab; float* out; long n, stride; int rows, blk0, tall; };
-struct RedGroup { RedSeg s[2 * PW_MAXP + RED_MAXX]; int nseg, accumulate; };
-
-// Block shape per segment: "wide" = 64 float4 columns x 4 row slices (few slab rows, many columns), "tall" = 16 columns
-// x 16 slices (hundreds of LayerNorm partial rows, 192 columns): keeps every thread's serial chain short either way.
-inline int red_blocks(long n, int tall) { return (int)((n + (tall ? 63 : 255)) / (tall ? 64 : 256)); }
-
-__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const RedGroup g) {
-  __shared__ f32x4 part[256];
-  RedSeg sg = g.s[0];
-#pragma unroll
-  for (int i = 1; i < 2 * PW_MAXP + RED_MAXX; ++i)
-    if (i < g.nseg && (int)blockIdx.x >= g.s[i].blk0) sg = g.s[i];
-  const float* __restrict__ slab = sg.slab;
-  float* __restrict__ out = sg.out;
-  const long n = sg.n, stride = sg.stride;
-  const long blk = (long)blockIdx.x - sg.blk0;
-  const int rows = sg.rows, accumulate = g.accumulate;
-  const int ncol = sg.tall ? 16 : 64, nsl = 256 / ncol;
-  const int col = threadIdx.x % ncol, sl = threadIdx.x / ncol;
-  const long i = (blk * ncol + col) * 4;
-  f32x4 s = {0.f, 0.f, 0.f, 0.f};
-  if (i + 4 <= n) {
-#pragma unroll 8
-    for (int sp = sl; sp < rows; sp += nsl) s += *reinterpret_cast<const f32x4*>(slab + (long)sp * stride + i);
-  } else if (i < n) {
-    for (int sp = sl; sp < rows; sp += nsl)
-      for (int e = 0; e < 4 && i + e < n; ++e) s[e] += slab[(long)sp * stride + i + e];
-  }
-  part[sl * ncol + col] = s;
-  __syncthreads();
-  if (sl == 0 && i < n) {
-    f32x4 t = part[col];
-    for (int k = 1; k < nsl; ++k) t += part[k * ncol + col];
-    if (i + 4 <= n) {
-      f32x4* o = reinterpret_cast<f32x4*>(out + i);
-      *o = accumulate ? *o + t : t;
-    } else {
-      for (int e = 0; e < 4 && i + e < n; ++e) out[i + e] = accumulate ? out[i + e] + t[e] : t[e];
-    }
-  }
+// out[i] (+)= sum_s slab[s][i] for up to 2*PW_MAXP segments (weights and biases of a group) + RED_MAXX extra ones in ONE
+// launch, one workgroup per virtual block: the arithmetic and the block shapes are in wgrad_reduce.h.
+static_assert(RED_MAXP == PW_MAXP, "a reduce job holds the segments of one group");
+__global__ __launch_bounds__(RED_THREADS) void wgrad_reduce_kernel(const RedGroup g) {
+  __shared__ f32x4 part[RED_THREADS];
+  red_block(g, (int)blockIdx.x, part);
 }
 
 struct WgradPlan { int tk, mc, tiles_n, tiles_k, splits, rows_per_split; };
@@ -518,9 +480,10 @@ inline size_t shared_ws_floats(int M, int N, int K) {
 unsigned long long* g_wstamps = nullptr;
 #endif
 
-int launch_reduce(const RedGroup& rg, int nblk, hipStream_t st) {
+int launch_reduce(const RedGroup& rg, hipStream_t st) {
+  if (rg.nblk <= 0) return IQ_OK;
   IQ_PROF(IQ_FAM_WGRAD, st);
-  wgrad_reduce_kernel<<<nblk, 256, 0, st>>>(rg);
+  wgrad_reduce_kernel<<<rg.nblk, RED_THREADS, 0, st>>>(rg);
   // (no algorithmic bytes of its own: the gradient it writes is counted with the partial-tile kernel; its slab traffic exists
   //  because of the M-split and shows up as this launch's time)
   IQ_PROF_K(0.0, 0.0, "wgrad_reduce_kernel");
@@ -567,12 +530,13 @@ int wgrad_shared_one(const iq_wgrad_problem_t& pb, int M, float* ws, int accumul
   RedGroup rg;
   memset(&rg, 0, sizeof(rg));
   const long n = (long)N * K;
-  rg.s[0] = RedSeg{q.slab, pb.dW, n, n, w.splits, 0, 0};
+  rg.seg[0] = RedSeg{q.slab, pb.dW, n, n, w.splits, 0, 0};
   int nblk = (int)((n + 255) / 256);
   rg.nseg = 1;
-  if (pb.dbias) { rg.s[1] = RedSeg{q.bslab, pb.dbias, (long)N, (long)N, w.splits, nblk, 0}; nblk += (N + 255) / 256; rg.nseg = 2; }
+  if (pb.dbias) { rg.seg[1] = RedSeg{q.bslab, pb.dbias, (long)N, (long)N, w.splits, nblk, 0}; nblk += (N + 255) / 256; rg.nseg = 2; }
   rg.accumulate = accumulate;
-  return launch_reduce(rg, nblk, st);
+  rg.nblk = nblk;
+  return launch_reduce(rg, st);
 }
 
 }  // namespace
@@ -604,9 +568,26 @@ extern "C" size_t iq_wgrad_grouped_ws_bytes(const iq_wgrad_problem_t* probs, int
   return mx * sizeof(float);
 }
 
+extern "C" int iq_reduce_job_run(const iq_reduce_job_t* job, iq_stream_t stream) {
+  if (!job || job->nblk < 0 || job->nseg < 0 || job->nseg > IQ_REDUCE_JOB_SEGS) return IQ_ERR_ARG;
+  launch_reduce(*job, (hipStream_t)stream);
+  return iq_launch_status();
+}
+
 extern "C" int iq_gemm_bf16_wgrad_grouped(const iq_wgrad_problem_t* probs, int nprob, int M, float* ws, size_t ws_bytes,
                                           int accumulate, int max_workgroups, const iq_reduce_seg_t* extra, int nextra,
                                           iq_stream_t stream) {
+  iq_reduce_job_t job;
+  const int rc = iq_gemm_bf16_wgrad_grouped_deferred(probs, nprob, M, ws, ws_bytes, accumulate, max_workgroups, extra, nextra, &job, stream);
+  return rc != IQ_OK ? rc : iq_reduce_job_run(&job, stream);
+}
+
+// The partial-tile launch of the group; its slab reduce (+ the extra segments) is handed back in *job instead of launched.
+extern "C" int iq_gemm_bf16_wgrad_grouped_deferred(const iq_wgrad_problem_t* probs, int nprob, int M, float* ws, size_t ws_bytes,
+                                                   int accumulate, int max_workgroups, const iq_reduce_seg_t* extra, int nextra,
+                                                   iq_reduce_job_t* job, iq_stream_t stream) {
+  if (!job) return IQ_ERR_ARG;
+  memset(job, 0, sizeof(*job));
   if (nextra < 0 || nextra > RED_MAXX || (nextra > 0 && !extra)) return IQ_ERR_ARG;
   for (int i = 0; i < nextra; ++i)
     if (!extra[i].partials || !extra[i].out || extra[i].rows <= 0 || extra[i].n <= 0 || extra[i].row_stride < extra[i].n ||
@@ -615,7 +596,7 @@ extern "C" int iq_gemm_bf16_wgrad_grouped(const iq_wgrad_problem_t* probs, int n
   auto add_extra = [&](RedGroup& rg, int& nblk) {
     for (int i = 0; i < nextra; ++i) {
       const int tall = extra[i].rows >= 64;
-      rg.s[rg.nseg++] = RedSeg{extra[i].partials, extra[i].out, (long)extra[i].n, (long)extra[i].row_stride, extra[i].rows, nblk, tall};
+      rg.seg[rg.nseg++] = RedSeg{extra[i].partials, extra[i].out, (long)extra[i].n, (long)extra[i].row_stride, extra[i].rows, nblk, tall};
       nblk += red_blocks(extra[i].n, tall);
     }
   };
@@ -645,16 +626,17 @@ extern "C" int iq_gemm_bf16_wgrad_grouped(const iq_wgrad_problem_t* probs, int n
     int nblk = 0;
     for (int i = 0; i < nprob; ++i) {
       const long n = (long)probs[i].N * probs[i].K;
-      rg.s[rg.nseg++] = RedSeg{slab[i], probs[i].dW, n, (long)pad4((size_t)n), wb.splits, nblk, 0};
+      rg.seg[rg.nseg++] = RedSeg{slab[i], probs[i].dW, n, (long)pad4((size_t)n), wb.splits, nblk, 0};
       nblk += (int)((n + 255) / 256);
       if (probs[i].dbias) {
-        rg.s[rg.nseg++] = RedSeg{bslab[i], probs[i].dbias, (long)probs[i].N, (long)pad4(probs[i].N), wb.splits, nblk, 0};
+        rg.seg[rg.nseg++] = RedSeg{bslab[i], probs[i].dbias, (long)probs[i].N, (long)pad4(probs[i].N), wb.splits, nblk, 0};
         nblk += (probs[i].N + 255) / 256;
       }
     }
     add_extra(rg, nblk);
     rg.accumulate = accumulate;
-    launch_reduce(rg, nblk, st);
+    rg.nblk = nblk;
+    *job = rg;
     return iq_launch_status();
   }
   if (!group_is_pw(probs, nprob)) {
@@ -667,13 +649,15 @@ extern "C" int iq_gemm_bf16_wgrad_grouped(const iq_wgrad_problem_t* probs, int n
       }
       if (rc != IQ_OK) return rc;
     }
+    // (those reduces cannot wait: the next problem overwrites the slab area they read.  The extra segments can.)
     if (nextra > 0) {
       RedGroup rg;
       memset(&rg, 0, sizeof(rg));
       int nblk = 0;
       add_extra(rg, nblk);
       rg.accumulate = accumulate;
-      launch_reduce(rg, nblk, st);
+      rg.nblk = nblk;
+      *job = rg;
     }
     return iq_launch_status();
   }
@@ -699,11 +683,11 @@ extern "C" int iq_gemm_bf16_wgrad_grouped(const iq_wgrad_problem_t* probs, int n
     tile0 += q.tiles_n * q.tiles_k;
     const long n = (long)b.N * b.K;
     q.slab = cur; cur += (size_t)w.splits * pad4((size_t)n);
-    rg.s[rg.nseg++] = RedSeg{q.slab, b.dW, n, n, w.splits, nblk, 0};
+    rg.seg[rg.nseg++] = RedSeg{q.slab, b.dW, n, n, w.splits, nblk, 0};
     nblk += (int)((n + 255) / 256);
     if (b.dbias) {
       q.bslab = cur; cur += (size_t)w.splits * pad4(b.N);
-      rg.s[rg.nseg++] = RedSeg{q.bslab, b.dbias, (long)b.N, (long)b.N, w.splits, nblk, 0};
+      rg.seg[rg.nseg++] = RedSeg{q.bslab, b.dbias, (long)b.N, (long)b.N, w.splits, nblk, 0};
       nblk += (b.N + 255) / 256;
     }
   }
@@ -716,7 +700,8 @@ extern "C" int iq_gemm_bf16_wgrad_grouped(const iq_wgrad_problem_t* probs, int n
     wgrad_pw_kernel<<<w.ntile * w.splits, PW_THREADS, lds_pw, st>>>(g);
     IQ_PROF_K(wbytes, wflops, "wgrad_pw_kernel");
   }
-  launch_reduce(rg, nblk, st);
+  rg.nblk = nblk;
+  *job = rg;
   return iq_launch_status();
 }
 

@@ -53,7 +53,7 @@ struct WsPlan {
   size_t step_ctr, patches, x0, head_feat, head_stat;
   struct L { size_t qkv, att, lse, z1, mean1, rstd1, x1, hid, gate, z2, mean2, rstd2, x2; };
   std::vector<L> layers;
-  size_t gA, gB, gAtt, demb, wgrad_ws, wgrad_ws_bytes, ln_part[2], embw_scratch;
+  size_t gA, gB, gAtt, demb, wgrad_ws, wgrad_ws_bytes, ln_part[3], embw_scratch;   // ln_part: norm2 of even layers | norm1 | norm2 of odd layers
   // dY operands of a layer's weight gradients (live from their producer to the layer's grouped weight-gradient launch)
   size_t gZ, gY, gZ1, gY1, gH, gQKV;
   size_t total;
@@ -259,7 +259,9 @@ WsPlan plan_ws(const iq_model* m, int B) {
   if ((size_t)iq_ffn_chain_bwd_partial_rows((int)M) > ln_rows_fused) ln_rows_fused = (size_t)iq_ffn_chain_bwd_partial_rows((int)M);
   ln_rows_fused *= 2 * D * sizeof(float);
   const size_t ln_bytes = ln_rows_fused > iq_ln_bwd_ws_bytes((int)D) ? ln_rows_fused : iq_ln_bwd_ws_bytes((int)D);
-  for (int k = 0; k < 2; ++k) w.ln_part[k] = take(ln_bytes);
+  // (norm2's twice, by layer parity: a layer's rows are still read by its reduce, riding in the launch that writes the
+  // rows of the layer below -- backward_impl)
+  for (int k = 0; k < 3; ++k) w.ln_part[k] = take(ln_bytes);
   w.embw_scratch = take((size_t)D * m->Ppad * 4 + 256);
   w.total = cur;
   return w;
@@ -719,7 +721,10 @@ static int backward_impl(iq_model_t* m, const float* dlogits, const float* denc,
     unsigned char *gZ = ws + w.gZ, *gY = ws + w.gY, *gZ1 = ws + w.gZ1, *gY1 = ws + w.gY1;
     unsigned char *gH = ws + w.gH, *gQKV = ws + w.gQKV;
     iq_epilogue_t e;
-    float* lp2 = (float*)(ws + w.ln_part[0]);
+    // norm2's partial rows alternate between two buffers by layer parity: whoever writes layer l's (iq_ln_bwd here for the top
+    // layer, the layer above's q,k,v data-gradient launch, this layer's chain launch) and whoever reads them (lnseg) agree
+    auto ln2_part = [&](int layer) { return (float*)(ws + w.ln_part[(layer & 1) ? 2 : 0]); };
+    float* lp2 = ln2_part(l);
     float* lp1 = (float*)(ws + w.ln_part[1]);
     // norm2 backward (+ regenerated dropout2 mask) -- unless the layer above already did it in its QKV data gradient
     const bool norm2_here = l == Lr - 1 || !fuse2;
@@ -785,19 +790,37 @@ static int backward_impl(iq_model_t* m, const float* dlogits, const float* denc,
       if (l == 0) break;
     }
     IQ_TRY(iq_attn_bwd(ws + a.qkv, ws + a.att, ws + w.gAtt, (const float*)(ws + a.lse), gQKV, B, S, H, m->dh, stream), "attention bwd");
-    // The four weight gradients of the layer, BEFORE the QKV data gradient: fused with the norm2 backward of the layer
-    // below, that GEMM overwrites gZ / gY and the norm2 partial rows, which the weight gradients / their reduce still read.
-    if (pgrads) IQ_TRY(iq_gemm_bf16_wgrad_grouped(wg, 4, M, wws, w.wgrad_ws_bytes, accumulate, 0, lnseg, 4, stream), "layer weight gradients");
-    // ... unless the layer below takes it into its own chain launch (iq_qkv_dgrad_ffn_chain_bwd)
+    // The layer below may take the QKV data gradient into its own chain launch (iq_qkv_dgrad_ffn_chain_bwd) ...
     deferred = l > 0 && fuse2 && chain && route.chain_takes_qkv_dgrad && sidx - 1 >= stage_lo;
+    // The four weight gradients of the layer, BEFORE the QKV data gradient: fused with the norm2 backward of the layer
+    // below, that GEMM overwrites gZ / gY, which the partial-tile kernel of the weight gradients still reads.
+    // Where that GEMM is a launch of this iteration, the slab reduce (+ the LayerNorm rows) does not get a launch of its
+    // own: it rides in the GEMM's launch, on the workgroup slots its row tiles leave free (iq_gemm_bf16_lnbwd_ride; cfg B:
+    // 394 tiles on 512 slots).  Nothing on the data-gradient chain reads the gradients, so nothing waits for it.  What the
+    // reduce reads while the tiles write:
+    //   - the norm2 partial rows: the tiles write those of the layer BELOW, which live in the other buffer (ln2_part);
+    //   - the norm1 partial rows, the slab area, the gradient buffer: their next writers (the chain / FFN1 launch and the
+    //     weight gradients of the layer below, the embedding's, the optimizer) are later launches on this stream;
+    //   - gZ / gY, which the tiles overwrite, are operands of the partial-tile kernel, not of the reduce, and that kernel
+    //     has finished before the GEMM's launch begins.
+    // A stage range (DDP bucket) ends with the GEMM of its last iteration, so its gradients are complete when it returns.
+    const bool ride = pgrads && l > 0 && fuse2 && !deferred;
+    iq_reduce_job_t job;
+    if (ride) {
+      IQ_TRY(iq_gemm_bf16_wgrad_grouped_deferred(wg, 4, M, wws, w.wgrad_ws_bytes, accumulate, 0, lnseg, 4, &job, stream),
+             "layer weight gradients (partial tiles)");
+    } else if (pgrads) {
+      IQ_TRY(iq_gemm_bf16_wgrad_grouped(wg, 4, M, wws, w.wgrad_ws_bytes, accumulate, 0, lnseg, 4, stream), "layer weight gradients");
+    }
     if (deferred) continue;
     if (l > 0 && fuse2) {
       const LayerOff& ob = m->L[l - 1];
       const WsPlan::L& ab = w.layers[l - 1];
       const iq_dropout_t dr2b = m->bwd_site(3 + 3 * (l - 1), step_dev, tr);
-      IQ_TRY(iq_gemm_bf16_lnbwd(gQKV, 3 * D, m->sht(o.t_wqkv), 3 * D, gZ1, D, ws + ab.z2, (const float*)(ws + ab.mean2),
-                                (const float*)(ws + ab.rstd2), P + ob.g2, &dr2b, gZ, gY, lp2, M, D, 3 * D, stream),
-             "qkv dgrad + norm2 bwd of the layer below");
+      IQ_TRY(iq_gemm_bf16_lnbwd_ride(gQKV, 3 * D, m->sht(o.t_wqkv), 3 * D, gZ1, D, ws + ab.z2, (const float*)(ws + ab.mean2),
+                                     (const float*)(ws + ab.rstd2), P + ob.g2, &dr2b, gZ, gY, ln2_part(l - 1), M, D, 3 * D,
+                                     ride ? &job : nullptr, stream),
+             "qkv dgrad + norm2 bwd of the layer below (+ this layer's slab reduce)");
     } else {
       memset(&e, 0, sizeof(e));
       e.residual = gZ1; e.ldr = D;
