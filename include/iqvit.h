@@ -546,7 +546,34 @@ int iq_frames_spectrogram_bwd(const float* x, const float* table, const float* d
  * 64 KB + 3 KB + 64.25 KB of 160 KB), so nothing else is refused.  n_frames <= 0: success, nothing is launched.
  * Launch shape (the image is the same bit for bit): with chunks = ceil(columns / 32), when 4 * (2 len rounded up to 4 + 3 Np +
  * chunks * 64 (Np + 1) + 64 Np) bytes <= 144 KB one workgroup per frame keeps all of Y in LDS and takes the bands of 32 channels
- * in turn; otherwise one workgroup per (frame, band) holds 32 columns of Y at a time and recomputes X for its band. */
+ * in turn; otherwise one workgroup per (frame, band) holds 32 columns of Y at a time and recomputes X for its band.
+ * iq_frames_cyclic_bwd: dx[n_frames, 2, len] = the gradient of L = sum(out * dout) with respect to x; everything is recomputed
+ * from x (no workspace).  For a complex w, G_w = dL/dRe w + i dL/dIm w; rho[t,k] = rc[r] + i rs[r], so Y = X conj(rho).  Per
+ * channel an image element is one pair (k, l): SCF row of a = k - l, column of k: g[k,l] = dout there; conjugate row of a =
+ * k + l, column of k: gc[k,l].  P, Pc and den = D[k] D[l] inv2 + floor are symmetric in (k, l), so the two elements of a pair
+ * fold into one weight:
+ *   phi(P, den) = 1 (power),  1 / (ln 10 (P + floor)) (log),  1 / den (coherence)
+ *   u[k,l]  = scale (g[k,l] + g[l,k]) phi(P[k,l], den[k,l]),     uc[k,l] = scale (gc[k,l] + gc[l,k]) phi(Pc[k,l], den[k,l])
+ *   H[k,l]  = 2 inv2 u[k,l] S[k,l],                              Hc[k,l] = 2 inv2 uc[k,l] Sc[k,l]
+ *   gD[k]   = - inv2 sum_l scale [(g[k,l] + g[l,k]) P[k,l] + (gc[k,l] + gc[l,k]) Pc[k,l]] D[l] / den[k,l]^2   (coherence, else 0)
+ *   G_Y[t,k] = sum_l H[k,l] Y[t,l] + sum_l Hc[k,l] conj(Y[t,l]) + 2 gD[k] Y[t,k]
+ *   G_X[t,k] = rho[t,k] G_Y[t,k]:  dRe = dYre rc - dYim rs,  dIm = dYre rs + dYim rc   (the transpose of the forward's rotation
+ *              for ANY table values)
+ *   G_z[j]   = sum over the windows t and offsets m with j0(t) + m = j of sum_k (c[m,k] + i s[m,k]) G_X[t,k]
+ *   dx[.,0,j] = Re G_z[j],  dx[.,1,j] = Im G_z[j]
+ * A kind with one channel drops the other channel's terms; columns at and behind `columns` and samples outside [0, len)
+ * contribute nothing; a sample no window covers gets exactly 0.  S, Sc, D and Y are the forward's, bit for bit.  Every element of
+ * dx is written exactly once, by one thread, after a gather in a fixed order (per band of 32 channels k, per 32 columns, the
+ * columns ascending; the sum over l of G_Y per wave over its l tiles, then (wave 0 + wave 2) + (wave 1 + wave 3)): no atomics,
+ * two runs agree bit for bit, a frame's gradient depends on neither n_frames nor its position.  Nothing but dx is written.
+ * Refusals as iq_frames_cyclic, in the same order, with dout and dx in the place of out: NULL dout / dx and dout / dx not
+ * 4-byte aligned are IQ_STATUS_ARG.  One workgroup holds the frame, its gradient, rot, D, 32 columns of Y and six 32 x 33 tiles
+ * in the CU's 160 KB of LDS, so IQ_STATUS_UNSUPPORTED also when
+ *   4 * (2 * (2 len rounded up to 4) + 67 Np + 6688) bytes > 160 KB
+ * (a function of len and Np alone, not of columns: at Np = 256 every len <= 4280 is taken, at Np = 32 every len <= 8032).
+ * n_frames <= 0: success, nothing is launched.  All of Y is kept in LDS when 4 * (2 * (2 len rounded up to 4) + 3 Np + 6624 +
+ * chunks * 64 (Np + 1)) bytes <= 160 KB; otherwise every band recomputes X chunk by chunk (the same arithmetic in the same
+ * order). */
 typedef struct iq_cyclic {
   int n_fft;      /* window length Np = image height = image width */
   int hop;        /* window t starts at sample t*hop - pad */
@@ -558,6 +585,8 @@ typedef struct iq_cyclic {
 } iq_cyclic_t;
 int iq_frames_cyclic(const float* x /*[n,2,len]*/, const float* table /*DEVICE [2,n_fft,n_fft]*/, const float* rot /*DEVICE [2,n_fft]*/,
                      float* out /*[n,C,n_fft,n_fft]*/, int n_frames, int len, const iq_cyclic_t* par, iq_stream_t stream);
+int iq_frames_cyclic_bwd(const float* x, const float* table, const float* rot, const float* dout /*[n,C,n_fft,n_fft]*/,
+                         float* dx /*[n,2,len]*/, int n_frames, int len, const iq_cyclic_t* par, iq_stream_t stream);
 int iq_patchify(const float* src, void* patches, int kind, int B, int C, int H, int W, int p, int Kpad,
                 iq_stream_t stream);
 int iq_cls_rows(const float* cls, const float* pe, void* x0, int B, int S, int D, const iq_dropout_t* drop,

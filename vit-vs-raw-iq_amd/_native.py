@@ -150,6 +150,7 @@ SIGNATURES = {
     "iq_frames_spectrogram": (_I, [_P, _P, _P, _I, _I, C.POINTER(Spectrogram), _P]),
     "iq_frames_spectrogram_bwd": (_I, [_P, _P, _P, _P, _I, _I, C.POINTER(Spectrogram), _P]),
     "iq_frames_cyclic": (_I, [_P, _P, _P, _P, _I, _I, C.POINTER(Cyclic), _P]),
+    "iq_frames_cyclic_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, C.POINTER(Cyclic), _P]),
     "iq_patchify": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "iq_cls_rows": (_I, [_P, _P, _P, _I, _I, _I, C.POINTER(Dropout), _P]),
     "iq_embed_bwd_gather": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, C.POINTER(Dropout), _I, _P]),

@@ -4,8 +4,8 @@
 //   every file    FR_* constants, frame_fits, frame_vec4, is_finite, launch_frames, red_sum
 //   transmitters  frame_key, draw_class_snr, rotate, noise4, scan_exclusive, frame_scale + store_frame (the generators' tail),
 //                 synth_lists_ok, pack_synth_lists
-//   channelizers  f32x16, acc_row, frame_floats, window_start, stage_frame, channel_step, power, scale_shift, image_value,
-//                 fft_size_ok
+//   channelizers  f32x16, acc_row, frame_floats, window_start, stage_frame, channel_step, overlap_add, power, scale_shift,
+//                 image_value, fft_size_ok
 #pragma once
 #include <math.h>
 
@@ -188,6 +188,32 @@ __device__ __forceinline__ void channel_step(f32x16& re, f32x16& im, float ac, f
   re = __builtin_amdgcn_mfma_f32_32x32x2f32(as, bq, re, 0, 0, 0);
   im = __builtin_amdgcn_mfma_f32_32x32x2f32(ac, bq, im, 0, 0, 0);
   im = __builtin_amdgcn_mfma_f32_32x32x2f32(-as, bi, im, 0, 0, 0);
+}
+
+// The last step of the channelizers' adjoints (spectrogram_bwd_kernel, cyclic_bwd_kernel): the overlap-add of one tile of
+// per-column products.  g holds G[m][c] for the window samples m in [mlo, mhi) (mlo a multiple of 32) of the columns t0 + c,
+// c < tcols, in segments of 32 samples: sample m at g + ((m - mlo) >> 5) * seg + (m & 31) * row + c; with PLANES = 2 the Q
+// product lies `plane` floats behind the I product and goes to dxq.  Thread j % FR_THREADS adds to sample j the products of
+// the columns whose window covers it, in ascending t: one owner per sample, no atomics, no dependence on timing.
+template <int PLANES>
+__device__ __forceinline__ void overlap_add(float* dxi, float* dxq, const float* g, int seg, int row, int plane, long t0,
+                                            int tcols, long hop, long pad, long mlo, long mhi, int len, int tid) {
+  long jlo = t0 * hop - pad + mlo, jhi = (t0 + tcols - 1) * hop - pad + mhi - 1;   // first and last sample touched
+  jlo = jlo < 0 ? 0 : jlo;
+  jhi = jhi > len - 1 ? len - 1 : jhi;
+  for (long j = jlo + ((tid - jlo) & (FR_THREADS - 1)); j <= jhi; j += FR_THREADS) {
+    float si = 0.f, sq = 0.f;
+    for (int c = 0; c < tcols; ++c) {
+      const long m = j + pad - (t0 + c) * hop;
+      if (m >= mlo && m < mhi) {
+        const float* e = g + (int)((m - mlo) >> 5) * seg + (int)(m & 31) * row + c;
+        si += e[0];
+        if (PLANES == 2) sq += e[plane];
+      }
+    }
+    dxi[j] += si;
+    if (PLANES == 2) dxq[j] += sq;
+  }
 }
 
 // The image value of one (re, im): power, the level (mode 0: the power, mode 1: log10(P + floor)), then v * scale + shift.

@@ -199,22 +199,7 @@ __global__ __launch_bounds__(FR_THREADS) void spectrogram_bwd_kernel(SpArgs a) {
         // ---- overlap-add: sample j takes G[m][t] of every column t of the tile with m = j + pad - t*hop in this segment group
         const long mlo = (long)ms * FR_WAVES * SP_TILE;
         const long mhi = mlo + FR_WAVES * SP_TILE < n ? mlo + FR_WAVES * SP_TILE : (long)n;
-        long jlo = t0 * hop - pad + mlo, jhi = (t0 + tcols - 1) * hop - pad + mhi - 1;   // first and last sample touched
-        jlo = jlo < 0 ? 0 : jlo;
-        jhi = jhi > len - 1 ? len - 1 : jhi;
-        for (long j = jlo + ((tid - jlo) & (FR_THREADS - 1)); j <= jhi; j += FR_THREADS) {
-          float si = 0.f, sq = 0.f;
-          for (int c = 0; c < tcols; ++c) {
-            const long m = j + pad - (t0 + c) * hop;
-            if (m >= mlo && m < mhi) {
-              const float* g = blocks + (int)((m - mlo) >> 5) * SP_BLOCK + (int)(m & 31) * SP_TS + c;
-              si += g[0];
-              sq += g[SP_TILE * SP_TS];
-            }
-          }
-          dxi[j] += si;
-          dxq[j] += sq;
-        }
+        overlap_add<2>(dxi, dxq, blocks, SP_BLOCK, SP_TS, SP_TILE * SP_TS, t0, tcols, hop, pad, mlo, mhi, len, tid);
       }
     }
   }

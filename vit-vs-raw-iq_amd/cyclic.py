@@ -5,8 +5,10 @@ cyclostationarity of a signal; the spectral correlation function (SCF) keeps it:
 copy of itself shifted in frequency by the symbol rate (a line at alpha = fs / sps), and a real constellation (BPSK, PAM) also
 with its own conjugate.  One HIP kernel (csrc/cyclic.hip, iq_frames_cyclic) computes the first stage of the FFT accumulation
 method: the spectrogram's channelizer, a phase reference per window, and the complex Gram matrices over time, both stages on
-the fp32-input MFMA, the channelized frame never leaving the CU.  There is no CPU path; `cyclic_reference` is the host fp64
-DEFINITION the tests compare against.  The adjoint is not implemented: an input that requires grad is refused.
+the fp32-input MFMA, the channelized frame never leaving the CU.  iq_frames_cyclic_bwd is its adjoint (everything recomputed
+from x, a deterministic gather, no atomics): a front end built with `differentiable=True` carries gradients down to the SIGNAL
+(x.grad, saliency, FGSM / PGD on the frame); the default still refuses an input that requires grad, as it always did.  There is
+no CPU path; `cyclic_reference` / `cyclic_reference_bwd` are the host fp64 DEFINITION the tests compare against.
 
 With z[j] = I[j] + i Q[j], Np = n_fft, T = columns and window t's first sample j0 = t*hop - pad (samples outside [0, len) count
 as zero):
@@ -22,13 +24,26 @@ Row rho holds cyclic bin a = (rho + Np/2) mod Np, column kappa channel k = (kapp
 channel reads l = (k - a) mod Np, the conjugate channel l = (a - k) mod Np.  Both tables are computed in fp64 and rounded to fp32
 once; the kernel treats them as plain numbers.
 
-  CyclicSpectrum(n_fft, length, hop, pad, columns, window, kind, mode, floor, scale, shift)   cs(x) -> image;  .fit;  .struct()
+The adjoint (written out in include/iqvit.h), with G_w = dL/dRe w + i dL/dIm w for L = sum(image * dout), rho = rc[r] + i rs[r],
+g[k,l] = dout at the SCF element of the pair (k, l) and gc[k,l] at the conjugate one:
+  u[k,l]   = scale (g[k,l] + g[l,k]) phi,  phi = 1 | 1 / (ln 10 (P + floor)) | 1 / den,  den = D[k] D[l] inv_norm^2 + floor
+  H[k,l]   = 2 inv_norm^2 u[k,l] S[k,l]   (Hc from gc, Pc, Sc likewise)
+  gD[k]    = -inv_norm^2 sum_l scale [(g[k,l] + g[l,k]) P + (gc[k,l] + gc[l,k]) Pc] D[l] / den^2   (coherence only)
+  G_Y[t,k] = sum_l H[k,l] Y[t,l] + Hc[k,l] conj(Y[t,l]) + 2 gD[k] Y[t,k],   G_X = rho G_Y
+  G_z[j]   = sum over (t, m) with j0 + m = j of sum_k w[m] exp(+2 pi i k m / Np) G_X[t,k];  dx = (Re G_z, Im G_z)
+The backward kernel keeps the frame AND its gradient in LDS: `differentiable=True` refuses (at construction) a geometry with
+4 * (2 * (2 length rounded up to 4) + 67 n_fft + 6688) bytes above 160 KB -- frames longer than 4280 samples at n_fft 256, than
+8032 at n_fft 32; every n_fft works up to 4096 samples.
+
+  CyclicSpectrum(n_fft, length, hop, pad, columns, window, kind, mode, floor, scale, shift, differentiable)
+                                                         cs(x) -> image;  .fit;  .struct()
   CyclicSpectrum.for_model(model, length, **kw)          n_fft and kind from the ViT's (square) image and its channels
-  cyclic_reference(x, cs)                                host fp64
+  cyclic_reference(x, cs), cyclic_reference_bwd(x, dout, cs)          host fp64
 """
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -39,15 +54,24 @@ from .spectrogram import FFT_STEP, MAX_FFT, MAX_LENGTH, MIN_FFT, WINDOWS, _fit, 
 
 KINDS = ("scf", "conj", "both")
 MODES = ("power", "log", "coherence")
+LDS_BYTES = 160 * 1024       # what one workgroup of the backward kernel may have
+
+
+def adjoint_lds_bytes(n_fft, length):
+    """LDS of iq_frames_cyclic_bwd at its smallest layout (include/iqvit.h): the frame, its gradient, rot, D, 32 columns of Y
+    and six 32 x 33 tiles."""
+    return 4 * (2 * ((2 * length + 3) & ~3) + 67 * n_fft + 6688)
 
 
 class CyclicSpectrum:
     """The geometry and scaling of one front end.  Defaults: hop = n_fft // 4, columns = every window that lies wholly inside
     the frame with that hop and pad (at least one), inv_norm = 1 / (columns * sum w^2).  Arguments are checked here, before any
-    device work; the tables go to a device at the first call for that device and stay there."""
+    device work; the tables go to a device at the first call for that device and stay there.  differentiable=False (the
+    default) refuses an input that requires grad; True sends such an input through iq_frames_cyclic_bwd on the way back (the
+    images are the same bit for bit either way)."""
 
     def __init__(self, n_fft, length=1024, hop=None, pad=0, columns=None, window="hann", kind="both", mode="coherence",
-                 floor=1e-6, scale=1.0, shift=0.0):
+                 floor=1e-6, scale=1.0, shift=0.0, differentiable=False):
         self.n_fft = _index(n_fft, "n_fft", MIN_FFT, MAX_FFT)
         if self.n_fft % FFT_STEP:
             raise ValueError(f"n_fft must be a multiple of {FFT_STEP}, got {n_fft!r}")
@@ -70,6 +94,13 @@ class CyclicSpectrum:
         if self.floor <= 0 or float(np.float32(self.floor)) <= 0:
             raise ValueError(f"floor must be positive (in fp32), got {floor!r}")
         self.scale, self.shift = _number(scale, "scale"), _number(shift, "shift")
+        if not isinstance(differentiable, bool):
+            raise TypeError(f"differentiable must be a bool, got {differentiable!r}")
+        if differentiable and adjoint_lds_bytes(self.n_fft, self.length) > LDS_BYTES:
+            raise ValueError(f"differentiable=True: the adjoint keeps the frame and its gradient in LDS and needs "
+                             f"{adjoint_lds_bytes(self.n_fft, self.length)} bytes at n_fft {self.n_fft}, length {self.length}; "
+                             f"a workgroup has {LDS_BYTES}")
+        self.differentiable = differentiable
         w = _window(window, self.n_fft)
         self.inv_norm = 1.0 / (self.columns * float(np.sum(w * w)))
         c, s = _twiddles(self.n_fft, w)
@@ -116,22 +147,17 @@ class CyclicSpectrum:
         if not x.is_cuda:
             raise N.IqError("CyclicSpectrum runs on the MI355X only: x is a CPU tensor and there is no CPU fallback "
                             "(cyclic_reference is the host definition used by the tests)")
-        if x.requires_grad and torch.is_grad_enabled():
-            raise RuntimeError("CyclicSpectrum is not differentiable: its adjoint is not implemented, pass x.detach() "
-                               "(a Spectrogram carries gradients down to the signal)")
+        if x.requires_grad and torch.is_grad_enabled() and not self.differentiable:
+            raise RuntimeError("this CyclicSpectrum is not differentiable: build it with differentiable=True for gradients "
+                               "down to the signal, or pass x.detach()")
 
     def __call__(self, x):
-        """x: device (B, 2, len) fp32 -> (B, channels, n_fft, n_fft) fp32 on the current stream, no host synchronisation."""
+        """x: device (B, 2, len) fp32 -> (B, channels, n_fft, n_fft) fp32 on the current stream, no host synchronisation;
+        with differentiable=True differentiable with respect to x."""
         self._check(x)
-        x = x.detach().contiguous().float()
-        B = x.shape[0]
-        out = torch.empty(B, self.channels, self.n_fft, self.n_fft, dtype=torch.float32, device=x.device)
-        par = self.struct()
-        if B > 0:
-            N.check(N.lib().iq_frames_cyclic(x.data_ptr(), self.table_on(x.device).data_ptr(), self.rot_on(x.device).data_ptr(),
-                                             out.data_ptr(), B, self.length, C.byref(par),
-                                             torch.cuda.current_stream(x.device).cuda_stream), "iq_frames_cyclic")
-        return out
+        if x.requires_grad and torch.is_grad_enabled():
+            return _CyclicFn.apply(x, self)
+        return _launch_fwd(x.detach(), self)[1]
 
     def fit(self, x_subset):
         """Set scale and shift so that the images of `x_subset` (device (B, 2, len)) have zero mean and unit standard deviation
@@ -142,19 +168,54 @@ class CyclicSpectrum:
     def __repr__(self):
         return (f"CyclicSpectrum(n_fft={self.n_fft}, length={self.length}, hop={self.hop}, pad={self.pad}, "
                 f"columns={self.columns}, window={self.window!r}, kind={self.kind!r}, mode={self.mode!r}, floor={self.floor}, "
-                f"scale={self.scale}, shift={self.shift})")
+                f"scale={self.scale}, shift={self.shift}, differentiable={self.differentiable})")
 
 
-def cyclic_reference(x, cs):
-    """The definition in fp64 on the host, from the formula (matrix products, no FFT).
-    x: (B, 2, len) -> float64 (B, channels, n_fft, n_fft)."""
+def _launch_fwd(x, cs):
+    x = x.contiguous().float()
+    B = x.shape[0]
+    out = torch.empty(B, cs.channels, cs.n_fft, cs.n_fft, dtype=torch.float32, device=x.device)
+    par = cs.struct()
+    if B > 0:
+        N.check(N.lib().iq_frames_cyclic(x.data_ptr(), cs.table_on(x.device).data_ptr(), cs.rot_on(x.device).data_ptr(),
+                                         out.data_ptr(), B, cs.length, C.byref(par),
+                                         torch.cuda.current_stream(x.device).cuda_stream), "iq_frames_cyclic")
+    return x, out
+
+
+class _CyclicFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, cs):
+        x, out = _launch_fwd(x, cs)
+        ctx.save_for_backward(x)
+        ctx.par = cs.struct()                    # the scaling of THIS call: fit() may change the object before backward
+        ctx.cs = cs
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        (x,) = ctx.saved_tensors
+        cs = ctx.cs
+        dout = dout.contiguous().float()
+        dx = torch.empty_like(x)
+        if x.shape[0] > 0:
+            N.check(N.lib().iq_frames_cyclic_bwd(x.data_ptr(), cs.table_on(x.device).data_ptr(), cs.rot_on(x.device).data_ptr(),
+                                                 dout.data_ptr(), dx.data_ptr(), x.shape[0], cs.length, C.byref(ctx.par),
+                                                 torch.cuda.current_stream(x.device).cuda_stream), "iq_frames_cyclic_bwd")
+        return dx, None
+
+
+def _channelized(x, cs, table=None, rot=None):
+    """Y (B, T, bins) of the definition in fp64 with what the adjoint needs beside it: E[m,k] = c - i s, conj(rho)[t,k], the
+    sample index (T, n) of every window element and the mask of those inside the frame.  table (2, n, n) / rot (2, n) replace
+    the fp64 tables of `cs` (the tests' integer cases)."""
     if not isinstance(cs, CyclicSpectrum):
         raise TypeError(f"cs must be a CyclicSpectrum, got {type(cs).__name__}")
     x = _host(x).astype(np.float64)
     if x.ndim != 3 or x.shape[1] != 2 or x.shape[2] != cs.length:
         raise ValueError(f"x must be (B, 2, {cs.length}), got {x.shape}")
     n, T = cs.n_fft, cs.columns
-    c, s = _twiddles(n, _window(cs.window, n))
+    c, s = _twiddles(n, _window(cs.window, n)) if table is None else np.asarray(table, dtype=np.float64)
     E = c - 1j * s                                                     # w[m] exp(-2 pi i k m / n)
     j0 = np.arange(T, dtype=np.int64) * cs.hop - cs.pad
     j = j0[:, None] + np.arange(n, dtype=np.int64)[None, :]
@@ -163,8 +224,20 @@ def cyclic_reference(x, cs):
     cols = np.where(inside[None], z[:, np.clip(j, 0, cs.length - 1)], 0.0)        # (B, T, n)
     X = cols @ E                                                       # (B, T, bins)
     r = (np.arange(n, dtype=np.int64)[None, :] * (j0 % n)[:, None]) % n           # (T, bins); numpy's % is non-negative
-    ang = 2.0 * np.pi * r / n
-    Y = X * (np.cos(ang) - 1j * np.sin(ang))[None]
+    if rot is None:
+        ang = 2.0 * np.pi * r / n
+        crho = np.cos(ang) - 1j * np.sin(ang)
+    else:
+        rot = np.asarray(rot, dtype=np.float64)
+        crho = rot[0][r] - 1j * rot[1][r]
+    return X * crho[None], E, crho, j, inside
+
+
+def cyclic_reference(x, cs):
+    """The definition in fp64 on the host, from the formula (matrix products, no FFT).
+    x: (B, 2, len) -> float64 (B, channels, n_fft, n_fft)."""
+    Y, _, _, _, _ = _channelized(x, cs)
+    n = cs.n_fft
     D = (Y.real ** 2 + Y.imag ** 2).sum(axis=1)                        # (B, bins)
     Yt = Y.transpose(0, 2, 1)                                          # (B, bins, T)
     inv2 = cs.inv_norm ** 2
@@ -185,3 +258,44 @@ def cyclic_reference(x, cs):
             v = P / (D[:, kk] * D[:, l] * inv2 + cs.floor)
         chans.append(v * cs.scale + cs.shift)
     return np.ascontiguousarray(np.stack(chans, axis=1))
+
+
+def cyclic_reference_bwd(x, dout, cs, table=None, rot=None):
+    """The analytic adjoint in fp64: the gradient of sum(cyclic_reference(x) * dout) with respect to x, from the formulae of
+    the module docstring.  dout: (B, channels, n_fft, n_fft) -> float64 (B, 2, len).  table (2, n_fft, n_fft) and rot (2, n_fft)
+    replace the fp64 tables of `cs` (any numbers: the tests' integer cases)."""
+    Y, E, crho, j, inside = _channelized(x, cs, table, rot)
+    n, B = cs.n_fft, Y.shape[0]
+    d = _host(dout).astype(np.float64)
+    if d.shape != (B, cs.channels, n, n):
+        raise ValueError(f"dout must be {(B, cs.channels, n, n)}, got {d.shape}")
+    D = (Y.real ** 2 + Y.imag ** 2).sum(axis=1)                        # (B, bins)
+    Yt = Y.transpose(0, 2, 1)
+    inv2 = cs.inv_norm ** 2
+    k, l = np.meshgrid(np.arange(n), np.arange(n), indexing="ij")
+    den = D[:, :, None] * D[:, None, :] * inv2 + cs.floor
+    GY = np.zeros_like(Y)
+    gD = np.zeros_like(D)
+    for ch, conj in enumerate(((False,), (True,), (False, True))[KINDS.index(cs.kind)]):
+        G = Yt @ (Y if conj else np.conj(Y))                           # S or Sc (B, k, l)
+        a = (k + l) % n if conj else (k - l) % n
+        g = d[:, ch, (a + n // 2) % n, (k + n // 2) % n]               # dout at the element of the pair (k, l)
+        w = cs.scale * (g + g.transpose(0, 2, 1))
+        P = (G.real ** 2 + G.imag ** 2) * inv2
+        if cs.mode == "power":
+            u = w
+        elif cs.mode == "log":
+            u = w / (math.log(10.0) * (P + cs.floor))
+        else:
+            u = w / den
+            gD -= inv2 * (w * P * D[:, None, :] / den ** 2).sum(axis=2)
+        H = 2.0 * inv2 * u * G
+        GY += (np.conj(Y) if conj else Y) @ H.transpose(0, 2, 1)       # sum_l H[k,l] Y[t,l]  resp.  Hc[k,l] conj(Y[t,l])
+    GY += 2.0 * gD[:, None, :] * Y
+    dz = (GY * np.conj(crho)[None]) @ np.conj(E).T                     # G_X = rho G_Y; (B, T, n samples of the window)
+    out = np.zeros((B, 2, cs.length))
+    for t in range(cs.columns):
+        ok = inside[t]
+        out[:, 0, j[t, ok]] += dz[:, t, ok].real                       # the indices of one column are distinct
+        out[:, 1, j[t, ok]] += dz[:, t, ok].imag
+    return out
