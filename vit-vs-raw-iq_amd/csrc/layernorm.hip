@@ -252,14 +252,16 @@ extern "C" int iq_ln_fwd(const void* z, const float* gamma, const float* beta, v
   if (!ln_shape(D, &s)) return IQ_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   IQ_PROF(IQ_FAM_LN_FWD, st);
-  IQ_PROF_K(2.0 * (double)M * D * 2 + 8.0 * M, 0.0, "ln_fwd_kernel(D=%d)", D);
+  const double bytes = 2.0 * (double)M * D * 2 + 8.0 * M;
   bool ok = ln_dispatch(s, [&](auto lpr, auto nv) {
     constexpr int LPR = decltype(lpr)::value, NV = decltype(nv)::value;
+    IQ_PROF_K(bytes, 0.0, "ln_fwd_kernel<%d, %d, false>", LPR, NV);
     ln_fwd_kernel<LPR, NV><<<ln_grid(M, (64 / LPR) * 4, LN_FWD_MAX_BLOCKS), LN_THREADS, 0, st>>>((const bf16*)z, gamma, beta, (bf16*)x, mean,
                                                                              rstd, M, D, eps);
   });
   if (!ok) ok = ln_dispatch_masked(D, [&](auto nv) {
     constexpr int NV = decltype(nv)::value;
+    IQ_PROF_K(bytes, 0.0, "ln_fwd_kernel<64, %d, true>", NV);
     ln_fwd_kernel<64, NV, true><<<ln_grid(M, 4, LN_FWD_MAX_BLOCKS), LN_THREADS, 0, st>>>((const bf16*)z, gamma, beta, (bf16*)x,
                                                                                          mean, rstd, M, D, eps);
   });
@@ -276,7 +278,7 @@ extern "C" int iq_ln_bwd_partial_rows(int M, int D) {
     constexpr int LPR = decltype(lpr)::value;
     rows = ln_grid(M, (64 / LPR) * 4);
   });
-  if (!ok) rows = ln_grid(M, 4);
+  if (!ok) rows = ln_masked_nv(D) > 0 ? ln_grid(M, 4) : 0;   // a width iq_ln_bwd refuses leaves no partial rows
   return rows;
 }
 
@@ -294,7 +296,7 @@ extern "C" int iq_ln_bwd(const void* dx, const void* z, const float* mean, const
   if (dropping && !dy) return IQ_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
   IQ_PROF(IQ_FAM_LN_BWD, st);
-  IQ_PROF_K(2.0 * (double)M * D * (3 + (dropping ? 1 : 0)) + 8.0 * M, 0.0, "ln_bwd_kernel(D=%d)", D);
+  const double bytes = 2.0 * (double)M * D * (3 + (dropping ? 1 : 0)) + 8.0 * M;
   int rc = IQ_OK;
   bool ok = ln_dispatch(s, [&](auto lpr, auto nv) {
     constexpr int LPR = decltype(lpr)::value, NV = decltype(nv)::value;
@@ -302,6 +304,7 @@ extern "C" int iq_ln_bwd(const void* dx, const void* z, const float* mean, const
     const int nblk = ln_grid(M, RPB);
     const size_t lds = (size_t)RPB * 2 * D * sizeof(float);
     if (lds > 160 * 1024) { rc = IQ_ERR_UNSUPPORTED; return; }
+    IQ_PROF_K(bytes, 0.0, "ln_bwd_kernel<%d, %d, %s, false>", LPR, NV, dropping ? "true" : "false");
     if (dropping) {
       auto k = ln_bwd_kernel<LPR, NV, true>;
       if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -320,6 +323,7 @@ extern "C" int iq_ln_bwd(const void* dx, const void* z, const float* mean, const
     constexpr int RPB = 4;
     const int nblk = ln_grid(M, RPB);
     const size_t lds = (size_t)RPB * 2 * D * sizeof(float);
+    IQ_PROF_K(bytes, 0.0, "ln_bwd_kernel<64, %d, %s, true>", NV, dropping ? "true" : "false");
     if (dropping)
       ln_bwd_kernel<64, NV, true, true><<<nblk, LN_THREADS, lds, st>>>((const bf16*)dx, (const bf16*)z, mean, rstd, gamma,
                                                                       (bf16*)dz, (bf16*)dy, rng, thresh, dscale, ws, M, D);
