@@ -642,7 +642,11 @@ __global__ __launch_bounds__(NT, 4) void attn_bwd_once_kernel(const bf16* __rest
   __syncthreads();
 
   // ---- phase A: wave owns 16 keys, sweeps queries; dV^T, dK^T in registers, dS into the image --------------------
-  for (int unit = wave; unit < nunit; unit += NW) {       // wave-uniform
+  // A wave owns at most ONE unit (nunit <= ONCE_MAX_SPAD / 16 <= NW): a branch, not a loop.  Written as a strided loop
+  // over units (whose back edge no wave ever takes) this kernel compiled to its cap of 128 VGPRs with 12 more spilled to
+  // scratch (52 B per lane); as a branch it takes 118 and no scratch: 3 us of 65 per launch (profiles/attn_loads.txt).
+  static_assert(ONCE_MAX_SPAD <= 16 * NW, "attn_bwd_once_kernel: one 16-key unit per wave");
+  if (const int unit = wave; unit < nunit) {              // wave-uniform
     bf16x8 kf[KS], vf[KS];
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
@@ -1218,6 +1222,7 @@ int launch_bwd(const void* qkv, const void* out, const void* dout, const float* 
 // attn_bwd_once_kernel: dh = 64, no mask, padded length <= 224 rows (one chunk), 1024 threads (512 measured slower:
 // profiles/attn_bwd_once.txt).
 constexpr int ONCE_THREADS = 1024;
+static_assert(ONCE_MAX_SPAD <= 16 * (ONCE_THREADS / 64), "attn_bwd_once_kernel: its waves own one 16-key unit each");
 inline bool use_once(int S, int dh, bool masked) { return !masked && dh == 64 && (S + 31) / 32 * 32 <= ONCE_MAX_SPAD; }
 template <int NT>
 int launch_bwd_once(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int B, int S, int H,
