@@ -1,7 +1,7 @@
 """fp64 references, restated launch rules and the checks of the attention kernels (csrc/attention.hip), importable on the
 CPU.  Nothing here comes from the code under test: the mathematics is scale_dot_product_attention.py:23-39 of the
 reference layer (softmax(q k^T / sqrt(dh) [masked_fill -10000]) v) and its closed-form backward, the launch rules are
-copied by hand from the host code with their source lines, and the checks compare tensors only.
+copied by hand from the host code with the names they have there, and the checks compare tensors only.
 
 Layout everywhere: qkv is the packed projection output [Bf * S, 3 D] (q | k | v, head h at columns h * dh), out / dout
 are [Bf * S, D]; the references work on [Bf, H, S, dh] blocks ("parts") and `parts_of` / `heads_of` convert.
@@ -9,13 +9,13 @@ are [Bf * S, D]; the references work on [Bf, H, S, dh] blocks ("parts") and `par
 Two references
   attn_fp64      the exact mathematics in fp64.
   attn_rounded   the same in fp64 with a round-to-nearest-even to bf16 wherever the kernels' MFMA operands and stored
-                 results pass through bf16 (lines of csrc/attention.hip):
-                   forward   p = exp2(s c - rowmax), rounded by pack_b before V^T P^T (l. 245-253, 880-890); the row sum
-                             l adds the UNROUNDED p (l. 247, 882); out = bf16(o / l) (l. 275, 907)
-                   backward  P = exp2(s c - lse2), rounded by pack_b before dO^T P (l. 393-404, 678-698, 1022-1031);
+                 results pass through bf16 (csrc/attention.hip; pack_b and rebuild_p_ds are csrc/attn_common.h's):
+                   forward   p = exp2(s c - rowmax), rounded by pack_b before V^T P^T (both forward kernels); the row sum
+                             l adds the UNROUNDED p (`rs += pv`); out = bf16(o / l) (`o * inv`)
+                   backward  P = exp2(s c - lse2), rounded by pack_b before dO^T P (phase A of the three backward kernels);
                              dS = P (dP - delta) scale uses the unrounded P and is rounded before Q^T dS and K^T dS
-                             (l. 396-405, 500-511, 681-699, 1025-1032, 1107-1113); delta = sum_d dO * out from the bf16
-                             out (l. 335, 635, 950); dQ, dK, dV stored as bf16 (l. 414, 524, 707, 746, 1044, 1126)
+                             (phases A and B); delta = sum_d dO * out from the bf16
+                             out (the `dl +=` loops); dQ, dK, dV stored as bf16 (the bf16x4 stores that end each phase)
                  The kernel's p is taken against the RUNNING maximum and rescaled by alpha in fp32; the model uses the row
                  maximum, which rounds the same number of values by the same relative step.  Rounding goes fp64 -> fp32 ->
                  bf16, as the kernels' values are fp32 when they are packed.
@@ -35,15 +35,15 @@ from collections import namedtuple
 import torch
 
 # ------------------------------------------------------------------------------------------------
-# launch rules of csrc/attention.hip, restated (line numbers of that file)
+# launch rules of csrc/attention.hip, restated (names of that file)
 # ------------------------------------------------------------------------------------------------
-FRAME_LDS_MAX = 112 * 1024        # ATT_FRAME_LDS_MAX, l. 1136
-FRAME_MAX_S = 128                 # use_frame, l. 1146
-FWD_BUDGET = 72 * 1024            # ATT_LDS_FWD_BUDGET, l. 1171
-BWD_BUDGET = 76 * 1024            # ATT_LDS_BWD_BUDGET, l. 1172
-MAX_S = 4096                      # ATT_MAX_S, l. 1173
-ONCE_MAX_SPAD = 224               # l. 549
-WAVES = 8                         # ATT_THREADS / 64, l. 37-38
+FRAME_LDS_MAX = 112 * 1024        # ATT_FRAME_LDS_MAX
+FRAME_MAX_S = 128                 # use_frame
+FWD_BUDGET = 72 * 1024            # ATT_LDS_FWD_BUDGET
+BWD_BUDGET = 76 * 1024            # ATT_LDS_BWD_BUDGET
+MAX_S = 4096                      # ATT_MAX_S
+ONCE_MAX_SPAD = 224               # ONCE_MAX_SPAD
+WAVES = 8                         # ATT_WAVES = ATT_THREADS / 64
 
 
 def spad_of(S):
@@ -51,58 +51,58 @@ def spad_of(S):
 
 
 def lds_ld(dh):
-    """AttCfg<DH>::LD, l. 49: LDS row stride in elements."""
+    """AttCfg<DH>::LD (csrc/attn_common.h): LDS row stride in elements."""
     return 16 if dh == 16 else dh + 16
 
 
 def frame_fwd_lds(S, H, dh):
-    """l. 1137-1140: one [spad][3 D + 16] bf16 image."""
+    """frame_fwd_lds: one [spad][3 D + 16] bf16 image."""
     return spad_of(S) * (3 * H * dh + 16) * 2
 
 
 def frame_bwd_lds(S, H, dh):
-    """l. 1141-1144: the qkv image, a [spad][D + 16] dO image and lse / delta [H][spad] fp32 each."""
+    """frame_bwd_lds: the qkv image, a [spad][D + 16] dO image and lse / delta [H][spad] fp32 each."""
     sp = spad_of(S)
     return sp * (3 * H * dh + 16) * 2 + sp * (H * dh + 16) * 2 + 2 * H * sp * 4
 
 
 def use_frame(S, lds):
-    """l. 1146."""
+    """use_frame."""
     return lds <= FRAME_LDS_MAX and S <= FRAME_MAX_S
 
 
 def use_once(S, dh, masked):
-    """l. 1221 (and l. 1300: only where the per-frame kernel does not claim the shape)."""
+    """use_once (and iq_attn_bwd_masked: only where the per-frame kernel does not claim the shape)."""
     return (not masked) and dh == 64 and spad_of(S) <= ONCE_MAX_SPAD
 
 
 def kchunk(S, dh):
-    """launch_fwd, l. 1192-1193: key rows staged at a time."""
+    """fwd_chunk_rows: key rows staged at a time."""
     return min(FWD_BUDGET // (2 * lds_ld(dh) * 2) // 32 * 32, spad_of(S))
 
 
 def bwd_chunk_rows(S, dh):
-    """l. 1176-1182: staged rows of the two-phase backward; lse / delta take 8 B per padded row out of the budget."""
+    """bwd_chunk_rows: staged rows of the two-phase backward; lse / delta take 8 B per padded row out of the budget."""
     room = BWD_BUDGET - 2 * spad_of(S) * 4
     return min(room // (2 * lds_ld(dh) * 2) // 32 * 32, spad_of(S))
 
 
 def expected_kernels(S, H, dh, masked):
-    """-> (forward kernel, backward kernel, forward stages, backward chunks): iq_attn_fwd_masked l. 1270-1284 and
-    iq_attn_bwd_masked l. 1299-1316."""
+    """-> (forward kernel, backward kernel, forward stages, backward chunks): iq_attn_fwd_masked and
+    iq_attn_bwd_masked."""
     tf = "true" if masked else "false"
     if not masked and use_frame(S, frame_fwd_lds(S, H, dh)):
         fwd, stages = f"attn_frame_fwd_kernel<{dh}>", 1
     else:
         kc = kchunk(S, dh)
-        fwd, stages = f"attn_fwd_kernel<{dh}, {tf}>", (S + kc - 1) // kc                # nstage, l. 155
+        fwd, stages = f"attn_fwd_kernel<{dh}, {tf}>", (S + kc - 1) // kc                # nstage
     if not masked and use_frame(S, frame_bwd_lds(S, H, dh)):
         bwd, chunks = f"attn_frame_bwd_kernel<{dh}>", 1
     elif use_once(S, dh, masked):
         bwd, chunks = "attn_bwd_once_kernel<1024>", 1
     else:
         ch = bwd_chunk_rows(S, dh)
-        bwd, chunks = f"attn_bwd_kernel<{dh}, {tf}>", (spad_of(S) + ch - 1) // ch       # nchunk, l. 317
+        bwd, chunks = f"attn_bwd_kernel<{dh}, {tf}>", (spad_of(S) + ch - 1) // ch       # nchunk
     return fwd, bwd, stages, chunks
 
 

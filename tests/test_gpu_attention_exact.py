@@ -30,14 +30,14 @@ everywhere.  Poisoned neighbours: frame 1 and head 1 filled with NaN, then +Inf:
 lse, dqkv keeps its bits.  Batch invariance: frame b of a Bf-frame launch equals a one-frame launch on its rows, also with
 600 frames (more workgroups than the chip holds at once).  Refusals leave the prefilled outputs alone and record nothing.
 
-Restated thresholds (attention_ref.py, with the lines of csrc/attention.hip):
-  per-frame kernels   S <= 128 and LDS <= 112 KiB (l. 1136, 1146); forward spad (3 D + 16) 2 B (l. 1137-1140); backward adds
-                      spad (D + 16) 2 B + 2 H spad 4 B (l. 1141-1144)
-  once kernel         dh = 64, no mask, spad <= 224, where the per-frame backward does not claim the shape (l. 1221, 1300)
+Restated thresholds (attention_ref.py, with their names in csrc/attention.hip):
+  per-frame kernels   S <= 128 and LDS <= 112 KiB (use_frame); forward spad (3 D + 16) 2 B (frame_fwd_lds); backward adds
+                      spad (D + 16) 2 B + 2 H spad 4 B (frame_bwd_lds)
+  once kernel         dh = 64, no mask, spad <= 224, where the per-frame backward does not claim the shape (use_once)
   forward stage       kchunk = 72 KiB / (2 images * LD * 2 B), down to 32 rows: 224 / 384 / 1152 rows at dh 64 / 32 / 16
-                      (l. 1171, 1192-1193); LD = dh + 16, or 16 at dh = 16 (l. 49)
-  backward chunk      (76 KiB - 8 B * spad) / (2 * LD * 2 B), down to 32 rows (l. 1172, 1176-1182)
-  refusals            S > 4096 or dh not in {16, 32, 64}: IQ_ERR_UNSUPPORTED before anything is recorded (l. 1257-1260, 1267, 1296)
+                      (fwd_chunk_rows); LD = dh + 16, or 16 at dh = 16 (AttCfg)
+  backward chunk      (76 KiB - 8 B * spad) / (2 * LD * 2 B), down to 32 rows (bwd_chunk_rows)
+  refusals            S > 4096 or dh not in {16, 32, 64}: IQ_ERR_UNSUPPORTED before anything is recorded (iq_attn_supported)
 The edge shapes below are derived from these rules at collection time, and both sides of each edge assert their kernel.
 
 Self-checks (tests/test_attention_ref_cpu.py; each applies a hand-made error to reference outputs on the CPU and requires the

@@ -17,10 +17,8 @@
 //   backward phase A ("key on the lane"):
 //        S[q,key] = Q K^T ;   P, dS -> B operands of dV^T[d,key] = dO^T P and dK^T = Q^T dS
 // The only transposed operands (V^T, K^T, dO^T, Q^T) come from row-major LDS images through
-// ds_read_b64_tr_b16.  K-slot order inside an MFMA is free as long as A and B agree: lane group g
-// uses rows {4g..4g+3} U {16+4g..16+4g+3} of each 32-row step, which is what two stacked 16x16
-// accumulator tiles hold and what tr_frag() fetches.
-// LDS images are [rows][dh+16] bf16 (32 B pad: conflict-free transposed reads, 2-way on row reads).
+// tr_frag().  The image layouts, the fragment loads and the constants are attn_common.h's, shared
+// with the read-back kernels of attn_maps.hip.
 // Softmax statistics fp32, exp2 domain.  dh in {16,32,64}; dh=16 zero-pads the QK^T contraction.
 //
 // Backward kernels: attn_bwd_once_kernel (dh = 64, no mask, padded length <= 224: the ViT shapes) forms S, P, dP and dS
@@ -28,7 +26,7 @@
 // per CU); attn_bwd_kernel (every other shape: masked, chunked, dh 16 / 32) recomputes them in phase B (7 products);
 // attn_frame_bwd_kernel takes short sequences one frame per workgroup.
 
-#include "common.h"
+#include "attn_common.h"
 #include "iqvit.h"
 #include "prof.h"
 
@@ -36,41 +34,7 @@ namespace {
 
 constexpr int ATT_THREADS = 512;   // 8 waves: S=197 has 7 blocks of 32 -> one pass per phase
 constexpr int ATT_WAVES = ATT_THREADS / 64;
-constexpr float LOG2E = 1.4426950408889634f;
-constexpr float LN2 = 0.6931471805599453f;
-constexpr float NEG_BIG = -1.0e30f;
 
-// exp2 for softmax arguments (<= 0 after the max / LSE subtraction): the bare v_exp_f32.  exp2f() wraps it in a
-// denormal-range fix-up (compare, select, add, select, ldexp: five extra VALU instructions per value) that only matters
-// for results below 2^-126, which are zero for every purpose here -- and the attention kernels are VALU-bound.
-__device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
-
-template <int DH> struct AttCfg {
-  static constexpr int LD = (DH == 16) ? 16 : DH + 16;  // LDS row stride (elements)
-  static constexpr int KS = (DH + 31) / 32;              // 32-deep contraction steps over d
-  static constexpr int DT = DH / 16;                     // 16-wide d tiles
-  static constexpr int CPR = DH / 8;                     // 16 B chunks per row
-};
-
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
-__device__ __forceinline__ bf16x8 tr_frag(const bf16* tile, int ld, int r0, int c0, int lane) {
-  const int i16 = lane & 15, g = lane >> 4;
-  const bf16* a = tile + (r0 + 4 * g + (i16 >> 2)) * ld + c0 + 4 * (i16 & 3);
-  s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(a));
-  s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(a + 16 * ld));
-  s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8, v);
-}
-
-// row-major fragment: 8 consecutive d of row `row`, contraction step s (d0 = 32 s + 8 g)
-template <int DH>
-__device__ __forceinline__ bf16x8 row_frag_lds(const bf16* tile, int row, int s, int lane) {
-  const int d0 = s * 32 + 8 * (lane >> 4);
-  bf16x8 v = {};
-  if (DH >= 32 || d0 < DH) v = *reinterpret_cast<const bf16x8*>(tile + row * AttCfg<DH>::LD + d0);
-  return v;
-}
 template <int DH>
 __device__ __forceinline__ bf16x8 row_frag_gmem(const bf16* base, long ldg, int row, int nrows, int s, int lane) {
   const int d0 = s * 32 + 8 * (lane >> 4);
@@ -111,22 +75,6 @@ __device__ __forceinline__ void stage_pair(bf16* imgA, const bf16* baseA, long l
       }
     }
   }
-}
-
-__device__ __forceinline__ bf16x8 pack_b(const f32x4& lo, const f32x4& hi) {
-  bf16x8 v;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) { v[r] = (bf16)lo[r]; v[4 + r] = (bf16)hi[r]; }
-  return v;
-}
-
-__device__ __forceinline__ float group4_max(float v) {  // across lane groups (lanes l, l^16, l^32, l^48)
-  v = fmaxf(v, __shfl_xor(v, 16, 64));
-  return fmaxf(v, __shfl_xor(v, 32, 64));
-}
-__device__ __forceinline__ float group4_sum(float v) {
-  v += __shfl_xor(v, 16, 64);
-  return v + __shfl_xor(v, 32, 64);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -197,7 +145,7 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_fwd_kernel(const bf16* __res
             }
             bf16x8 kf[C::KS];
 #pragma unroll
-            for (int s = 0; s < C::KS; ++s) kf[s] = row_frag_lds<DH>(Ks, kb + kt * 16 + c16, s, lane);
+            for (int s = 0; s < C::KS; ++s) kf[s] = row_frag<DH>(Ks, HeadRows<DH>{}, kb + kt * 16 + c16, s, lane);
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
               f32x4 a = {0.f, 0.f, 0.f, 0.f};
@@ -254,7 +202,7 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_fwd_kernel(const bf16* __res
           }
 #pragma unroll
           for (int dt = 0; dt < C::DT; ++dt) {
-            const bf16x8 vt = tr_frag(Vs, C::LD, kb, dt * 16, lane);
+            const bf16x8 vt = tr_frag(Vs, HeadRows<DH>{}, kb, dt * 16, lane);
             o[0][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vt, pb[0], o[0][dt], 0, 0, 0);
             if (u1) o[1][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vt, pb[1], o[1][dt], 0, 0, 0);
           }
@@ -377,8 +325,8 @@ __global__ __launch_bounds__(ATT_THREADS, 4) void attn_bwd_kernel(const bf16* __
           f32x4 sa = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
           for (int s = 0; s < C::KS; ++s) {
-            const bf16x8 qa = row_frag_lds<DH>(I0, ql + u * 16 + c16, s, lane);
-            const bf16x8 da = row_frag_lds<DH>(I1, ql + u * 16 + c16, s, lane);
+            const bf16x8 qa = row_frag<DH>(I0, HeadRows<DH>{}, ql + u * 16 + c16, s, lane);
+            const bf16x8 da = row_frag<DH>(I1, HeadRows<DH>{}, ql + u * 16 + c16, s, lane);
             sa = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa, kf[s], sa, 0, 0, 0);
             dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(da, vf[s], dp, 0, 0, 0);
           }
@@ -399,8 +347,8 @@ __global__ __launch_bounds__(ATT_THREADS, 4) void attn_bwd_kernel(const bf16* __
         const bf16x8 pB = pack_b(p[0], p[1]), dsB = pack_b(ds[0], ds[1]);
 #pragma unroll
         for (int dt = 0; dt < C::DT; ++dt) {
-          const bf16x8 doT = tr_frag(I1, C::LD, ql, dt * 16, lane);
-          const bf16x8 qT = tr_frag(I0, C::LD, ql, dt * 16, lane);
+          const bf16x8 doT = tr_frag(I1, HeadRows<DH>{}, ql, dt * 16, lane);
+          const bf16x8 qT = tr_frag(I0, HeadRows<DH>{}, ql, dt * 16, lane);
           dv[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(doT, pB, dv[dt], 0, 0, 0);
           dk[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qT, dsB, dk[dt], 0, 0, 0);
         }
@@ -429,8 +377,8 @@ __global__ __launch_bounds__(ATT_THREADS, 4) void attn_bwd_kernel(const bf16* __
 #pragma unroll
       for (int s = 0; s < C::KS; ++s) {
         const int q = min(wave, nblk - 1) * 32 + u * 16 + c16;
-        qf[u][s] = row_frag_lds<DH>(I0, q, s, lane);
-        dof[u][s] = row_frag_lds<DH>(I1, q, s, lane);
+        qf[u][s] = row_frag<DH>(I0, HeadRows<DH>{}, q, s, lane);
+        dof[u][s] = row_frag<DH>(I1, HeadRows<DH>{}, q, s, lane);
       }
   }
   for (int qg = 0; qg * ATT_WAVES < nblk; ++qg) {
@@ -475,8 +423,8 @@ __global__ __launch_bounds__(ATT_THREADS, 4) void attn_bwd_kernel(const bf16* __
           bf16x8 ka[C::KS], va[C::KS];
 #pragma unroll
           for (int s = 0; s < C::KS; ++s) {
-            ka[s] = row_frag_lds<DH>(I0, kl + kt * 16 + c16, s, lane);
-            va[s] = row_frag_lds<DH>(I1, kl + kt * 16 + c16, s, lane);
+            ka[s] = row_frag<DH>(I0, HeadRows<DH>{}, kl + kt * 16 + c16, s, lane);
+            va[s] = row_frag<DH>(I1, HeadRows<DH>{}, kl + kt * 16 + c16, s, lane);
           }
 #pragma unroll
           for (int u = 0; u < 2; ++u) {
@@ -506,7 +454,7 @@ __global__ __launch_bounds__(ATT_THREADS, 4) void attn_bwd_kernel(const bf16* __
         for (int u = 0; u < 2; ++u) dsB[u] = pack_b(ds[u][0], ds[u][1]);
 #pragma unroll
         for (int dt = 0; dt < C::DT; ++dt) {
-          const bf16x8 kT = tr_frag(I0, C::LD, kl, dt * 16, lane);
+          const bf16x8 kT = tr_frag(I0, HeadRows<DH>{}, kl, dt * 16, lane);
           dq[dt][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kT, dsB[0], dq[dt][0], 0, 0, 0);
           if (u1) dq[dt][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kT, dsB[1], dq[dt][1], 0, 0, 0);
         }
@@ -540,28 +488,12 @@ __global__ __launch_bounds__(ATT_THREADS, 4) void attn_bwd_kernel(const bf16* __
 // two 8-byte row reads of the image (the lane's k-slots are keys {4g..4g+3} U {16+4g..16+4g+3} of query c16: the slot
 // order, the operands and the summation order of attn_bwd_kernel's dQ product -- no cross-wave reduction, no atomics).
 // LDS at S = 197: dS image 224 x (13 x 16 keys + 8 pad) bf16 = 96,768 B, which leaves room for Q / dO only as unpadded
-// 128-byte rows (2 x 28,672 B) + lse / delta 1,792 B = 155,904 B: one workgroup per CU, so it has NT / 64 = 16 waves
-// (phase A: the 13 key units in one pass; phase B: the 13 sixteen-query halves in one pass), capped at 128 VGPRs.
-// 128-byte rows are XOR-swizzled: the 32-byte column pair p of row r lives at pair p ^ ((r >> 1) & 3).  A 32-lane half of a
-// transposed read covers 8 consecutive rows x 32 B, of a row read 16 lanes cover 16 rows x 16 B: either way every 16-byte
-// slot of the 256-byte bank row exactly once (conflict-free; the padded 160-byte rows were 2-way on row reads).  The dS row
-// stride is 32 * nunit + 16 bytes = 4 * odd dwords: 16 queries x {g, g + 1} fill the 64 banks once.
+// 128-byte rows (2 x 28,672 B) + lse / delta 1,792 B = 155,904 B (once_lds_bytes below): one workgroup per CU, so it has
+// NT / 64 = 16 waves (phase A: the 13 key units in one pass; phase B: the 13 sixteen-query halves in one pass), capped at
+// 128 VGPRs.
+// The 128-byte rows are XOR-swizzled (Swizzle64).  The dS row stride is 32 * nunit + 16 bytes = 4 * odd dwords: 16 queries x
+// {g, g + 1} fill the 64 banks once.
 constexpr int ONCE_MAX_SPAD = 224;
-constexpr int ONCE_LD = 64;       // Q / dO / K image row stride (elements): no pad, swizzled
-
-__device__ __forceinline__ int once_off(int row, int col) { return row * ONCE_LD + (col ^ (((row >> 1) & 3) << 4)); }
-
-__device__ __forceinline__ bf16x8 once_tr_frag(const bf16* tile, int r0, int dt, int lane) {
-  const int i16 = lane & 15, g = lane >> 4;
-  const bf16* a = tile + once_off(r0 + 4 * g + (i16 >> 2), dt * 16 + 4 * (i16 & 3));
-  s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(a));
-  s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(a + 16 * ONCE_LD));   // row + 16: same swizzle
-  s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8, v);
-}
-__device__ __forceinline__ bf16x8 once_row_frag(const bf16* tile, int row, int s, int lane) {
-  return *reinterpret_cast<const bf16x8*>(tile + once_off(row, s * 32 + 8 * (lane >> 4)));
-}
 
 // rows [0, spad) of NIMG [S, 64] head slices -> swizzled images, rows >= S zero-filled; all loads of a trip requested
 // before the first write (see stage_pair)
@@ -585,7 +517,7 @@ __device__ __forceinline__ void once_stage(bf16* const (&img)[NIMG], const bf16*
       if (id < total) {
         const bool live = r < S;
 #pragma unroll
-        for (int i = 0; i < NIMG; ++i) *reinterpret_cast<bf16x8*>(img[i] + once_off(r, c * 8)) = live ? v[i][j] : bf16x8{};
+        for (int i = 0; i < NIMG; ++i) *reinterpret_cast<bf16x8*>(Swizzle64{}(img[i], r, c * 8)) = live ? v[i][j] : bf16x8{};
       }
     }
   }
@@ -629,7 +561,7 @@ __global__ __launch_bounds__(NT, 4) void attn_bwd_once_kernel(const bf16* __rest
     if (q < S) {
 #pragma unroll
       for (int c = 0; c < 8; ++c) {
-        const bf16x8 a = *reinterpret_cast<const bf16x8*>(I1 + once_off(q, c * 8));
+        const bf16x8 a = *reinterpret_cast<const bf16x8*>(Swizzle64{}(I1, q, c * 8));
         const bf16x8 o8 = *reinterpret_cast<const bf16x8*>(ob + (long)q * D + c * 8);
 #pragma unroll
         for (int e = 0; e < 8; ++e) dl += (float)a[e] * (float)o8[e];
@@ -667,23 +599,15 @@ __global__ __launch_bounds__(NT, 4) void attn_bwd_once_kernel(const bf16* __rest
         f32x4 sa = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int s = 0; s < KS; ++s) {
-          const bf16x8 qa = once_row_frag(I0, ql + u * 16 + c16, s, lane);
-          const bf16x8 da = once_row_frag(I1, ql + u * 16 + c16, s, lane);
+          const bf16x8 qa = row_frag<DH>(I0, Swizzle64{}, ql + u * 16 + c16, s, lane);
+          const bf16x8 da = row_frag<DH>(I1, Swizzle64{}, ql + u * 16 + c16, s, lane);
           sa = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa, kf[s], sa, 0, 0, 0);
           dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(da, vf[s], dp, 0, 0, 0);
         }
         const f32x4 lq4 = *reinterpret_cast<const f32x4*>(lse_s + ql + u * 16 + 4 * g);
         const f32x4 dl4 = *reinterpret_cast<const f32x4*>(del_s + ql + u * 16 + 4 * g);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          // Padded QUERY rows need no mask: Q = dO = 0 and lse = delta = 0 there, so P = 1 and dS = 0 (finite: phase B
-          // reads those image rows for lanes whose result is not stored).  Padded KEYS do (only this wave's unit can hold
-          // them): P = exp2(-lse) is unbounded when a row's scores are all very negative, and inf * 0 would poison dQ.
-          float pv = fast_exp2(sa[r] * scale_log2 - lq4[r]);
-          if (unit_partial) pv = key < S ? pv : 0.f;
-          p[u][r] = pv;
-          ds[u][r] = pv * (dp[r] - dl4[r]) * scale;
-        }
+        // padded query rows give P = 1, dS = 0: finite, as phase B reads those image rows for lanes whose result is not stored
+        rebuild_p_ds(sa, dp, lq4, dl4, scale_log2, scale, unit_partial, key < S, p[u], ds[u]);
       }
       const bf16x8 pB = pack_b(p[0], p[1]), dsB = pack_b(ds[0], ds[1]);
       // the image holds what the dK product consumes; a half of pure padding queries is never read back (its 16-query
@@ -697,8 +621,8 @@ __global__ __launch_bounds__(NT, 4) void attn_bwd_once_kernel(const bf16* __rest
       }
 #pragma unroll
       for (int dt = 0; dt < DT; ++dt) {
-        const bf16x8 doT = once_tr_frag(I1, ql, dt, lane);
-        const bf16x8 qT = once_tr_frag(I0, ql, dt, lane);
+        const bf16x8 doT = tr_frag(I1, Swizzle64{}, ql, dt * 16, lane);
+        const bf16x8 qT = tr_frag(I0, Swizzle64{}, ql, dt * 16, lane);
         dv[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(doT, pB, dv[dt], 0, 0, 0);
         dk[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qT, dsB, dk[dt], 0, 0, 0);
       }
@@ -738,7 +662,7 @@ __global__ __launch_bounds__(NT, 4) void attn_bwd_once_kernel(const bf16* __rest
       const bf16x8 dsB = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
 #pragma unroll
       for (int dt = 0; dt < DT; ++dt) {
-        const bf16x8 kT = once_tr_frag(I0, kl, dt, lane);
+        const bf16x8 kT = tr_frag(I0, Swizzle64{}, kl, dt * 16, lane);
         dq[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kT, dsB, dq[dt], 0, 0, 0);
       }
     }
@@ -765,14 +689,6 @@ __global__ __launch_bounds__(NT, 4) void attn_bwd_once_kernel(const bf16* __rest
 // ds_read_b128 and the transposing ds_read_b64_tr_b16 are both conflict-free), and wave w then runs heads w, w + 8, ...
 // entirely on its own: same products, same orientation, same softmax arithmetic as the kernels above, no barrier after
 // the staging one.  Query / key halves that are pure padding (S = 65: rows 80..95) are skipped.
-template <int DH>
-__device__ __forceinline__ bf16x8 row_frag_img(const bf16* tile, int ld, int row, int s, int lane) {
-  const int d0 = s * 32 + 8 * (lane >> 4);
-  bf16x8 v = {};
-  if (DH >= 32 || d0 < DH) v = *reinterpret_cast<const bf16x8*>(tile + row * ld + d0);
-  return v;
-}
-
 // rows [0, spad) x `cols` elements (cols % 8 == 0) of a contiguous [S][cols] global block -> LDS image with row stride ld;
 // rows >= S are zero-filled.  UN loads in flight per thread.
 template <int UN>
@@ -831,7 +747,7 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_frame_fwd_kernel(const bf16*
           live[t][u] = q0 < S;
           m[t][u] = NEG_BIG; lsum[t][u] = 0.f;
 #pragma unroll
-          for (int s = 0; s < C::KS; ++s) qf[t][u][s] = row_frag_img<DH>(Qs, ld, min(q0 + c16, spad - 1), s, lane);
+          for (int s = 0; s < C::KS; ++s) qf[t][u][s] = row_frag<DH>(Qs, RowsRt{ld}, min(q0 + c16, spad - 1), s, lane);
 #pragma unroll
           for (int dt = 0; dt < C::DT; ++dt) o[t][u][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
@@ -841,9 +757,9 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_frame_fwd_kernel(const bf16*
 #pragma unroll
         for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
-          for (int s = 0; s < C::KS; ++s) kf[kt][s] = row_frag_img<DH>(Ks, ld, kb + kt * 16 + c16, s, lane);
+          for (int s = 0; s < C::KS; ++s) kf[kt][s] = row_frag<DH>(Ks, RowsRt{ld}, kb + kt * 16 + c16, s, lane);
 #pragma unroll
-        for (int dt = 0; dt < C::DT; ++dt) vt[dt] = tr_frag(Vs, ld, kb, dt * 16, lane);
+        for (int dt = 0; dt < C::DT; ++dt) vt[dt] = tr_frag(Vs, RowsRt{ld}, kb, dt * 16, lane);
 #pragma unroll
         for (int t = 0; t < G; ++t)
 #pragma unroll
@@ -979,8 +895,8 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_frame_bwd_kernel(const bf16*
         const int row = min((un0 + j) * 16 + c16, spad - 1);
 #pragma unroll
         for (int s = 0; s < C::KS; ++s) {
-          kf[j][s] = row_frag_img<DH>(Ks, ld, row, s, lane);
-          vf[j][s] = row_frag_img<DH>(Vs, ld, row, s, lane);
+          kf[j][s] = row_frag<DH>(Ks, RowsRt{ld}, row, s, lane);
+          vf[j][s] = row_frag<DH>(Vs, RowsRt{ld}, row, s, lane);
         }
 #pragma unroll
         for (int dt = 0; dt < C::DT; ++dt) { dv[j][dt] = f32x4{0.f, 0.f, 0.f, 0.f}; dk[j][dt] = f32x4{0.f, 0.f, 0.f, 0.f}; }
@@ -993,16 +909,16 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_frame_bwd_kernel(const bf16*
         for (int u = 0; u < 2; ++u) {
 #pragma unroll
           for (int s = 0; s < C::KS; ++s) {
-            qa[u][s] = row_frag_img<DH>(Qs, ld, ql + u * 16 + c16, s, lane);
-            da[u][s] = row_frag_img<DH>(Os, ldo, ql + u * 16 + c16, s, lane);
+            qa[u][s] = row_frag<DH>(Qs, RowsRt{ld}, ql + u * 16 + c16, s, lane);
+            da[u][s] = row_frag<DH>(Os, RowsRt{ldo}, ql + u * 16 + c16, s, lane);
           }
           lq4[u] = *reinterpret_cast<const f32x4*>(lq_s + ql + u * 16 + 4 * g);
           dl4[u] = *reinterpret_cast<const f32x4*>(dl_s + ql + u * 16 + 4 * g);
         }
 #pragma unroll
         for (int dt = 0; dt < C::DT; ++dt) {
-          doT[dt] = tr_frag(Os, ldo, ql, dt * 16, lane);
-          qT[dt] = tr_frag(Qs, ld, ql, dt * 16, lane);
+          doT[dt] = tr_frag(Os, RowsRt{ldo}, ql, dt * 16, lane);
+          qT[dt] = tr_frag(Qs, RowsRt{ld}, ql, dt * 16, lane);
         }
 #pragma unroll
         for (int j = 0; j < UG; ++j) {
@@ -1020,14 +936,7 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_frame_bwd_kernel(const bf16*
               sa = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa[u][s], kf[j][s], sa, 0, 0, 0);
               dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(da[u][s], vf[j][s], dp, 0, 0, 0);
             }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              // padded QUERY rows: Q = dO = 0 and lse = delta = 0, so P = 1 and dS = 0 multiply zeros; padded KEYS are masked
-              float pv = fast_exp2(sa[r] * scale_log2 - lq4[u][r]);
-              if (unit_partial) pv = key < S ? pv : 0.f;
-              p[u][r] = pv;
-              ds[u][r] = pv * (dp[r] - dl4[u][r]) * scale;
-            }
+            rebuild_p_ds(sa, dp, lq4[u], dl4[u], scale_log2, scale, unit_partial, key < S, p[u], ds[u]);
           }
           const bf16x8 pB = pack_b(p[0], p[1]), dsB = pack_b(ds[0], ds[1]);
 #pragma unroll
@@ -1067,8 +976,8 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_frame_bwd_kernel(const bf16*
           const int q = min(q0 + c16, spad - 1);
 #pragma unroll
           for (int s = 0; s < C::KS; ++s) {
-            qf[t][u][s] = row_frag_img<DH>(Qs, ld, q, s, lane);
-            dof[t][u][s] = row_frag_img<DH>(Os, ldo, q, s, lane);
+            qf[t][u][s] = row_frag<DH>(Qs, RowsRt{ld}, q, s, lane);
+            dof[t][u][s] = row_frag<DH>(Os, RowsRt{ldo}, q, s, lane);
           }
           lq[t][u] = lq_s[q];
           dl[t][u] = dl_s[q];
@@ -1083,11 +992,11 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_frame_bwd_kernel(const bf16*
         for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
           for (int s = 0; s < C::KS; ++s) {
-            ka[kt][s] = row_frag_img<DH>(Ks, ld, kl + kt * 16 + c16, s, lane);
-            va[kt][s] = row_frag_img<DH>(Vs, ld, kl + kt * 16 + c16, s, lane);
+            ka[kt][s] = row_frag<DH>(Ks, RowsRt{ld}, kl + kt * 16 + c16, s, lane);
+            va[kt][s] = row_frag<DH>(Vs, RowsRt{ld}, kl + kt * 16 + c16, s, lane);
           }
 #pragma unroll
-        for (int dt = 0; dt < C::DT; ++dt) kT[dt] = tr_frag(Ks, ld, kl, dt * 16, lane);
+        for (int dt = 0; dt < C::DT; ++dt) kT[dt] = tr_frag(Ks, RowsRt{ld}, kl, dt * 16, lane);
 #pragma unroll
         for (int t = 0; t < QG; ++t)
 #pragma unroll
@@ -1136,125 +1045,85 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_frame_bwd_kernel(const bf16*
   }
 }
 
-// LDS bytes of the per-frame kernels; 0 = not their shape (sequence too long for one image)
+// ---------------------------------------------------------------------------------------------
+// host: LDS byte counts (each decides its route and sizes its launch), routes, launches
+// ---------------------------------------------------------------------------------------------
 constexpr size_t ATT_FRAME_LDS_MAX = 112 * 1024;   // larger frames measured no faster than (frame, head) workgroups (profiles/r03_probes.txt)
-inline size_t frame_fwd_lds(int S, int H, int dh) {
-  const int spad = (S + 31) / 32 * 32;
-  return (size_t)spad * (3 * H * dh + 16) * 2;
-}
-inline size_t frame_bwd_lds(int S, int H, int dh) {
-  const int spad = (S + 31) / 32 * 32;
+constexpr size_t frame_fwd_lds(int S, int H, int dh) { return (size_t)padded32(S) * (3 * H * dh + 16) * 2; }
+constexpr size_t frame_bwd_lds(int S, int H, int dh) {
+  const int spad = padded32(S);
   return (size_t)spad * (3 * H * dh + 16) * 2 + (size_t)spad * (H * dh + 16) * 2 + (size_t)2 * H * spad * sizeof(float);
 }
 // Per-frame when the (frame, head) kernels would idle most of their 8 waves: at most 4 query tiles.
 inline bool use_frame(int S, size_t lds) { return lds <= ATT_FRAME_LDS_MAX && S <= 128; }
 
-template <int DH>
-int launch_frame_fwd(const void* qkv, void* out, float* lse, int B, int S, int H, hipStream_t st) {
-  const int spad = (S + 31) / 32 * 32;
-  const size_t lds = frame_fwd_lds(S, H, DH);
-  auto k = attn_frame_fwd_kernel<DH, (DH == 64 ? 2 : 4)>;
-  if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  const int threads = 64 * (H < ATT_WAVES ? H : ATT_WAVES);
-  k<<<B, threads, lds, st>>>((const bf16*)qkv, (bf16*)out, lse, S, H, spad, LOG2E / sqrtf((float)DH));
-  return iq_launch_status();
-}
-template <int DH>
-int launch_frame_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int B, int S, int H,
-                     hipStream_t st) {
-  const int spad = (S + 31) / 32 * 32;
-  const size_t lds = frame_bwd_lds(S, H, DH);
-  auto k = attn_frame_bwd_kernel<DH, (DH == 64 ? 2 : 3), (DH == 16 ? 4 : DH == 32 ? 3 : 2)>;
-  if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  const int threads = 64 * (H < ATT_WAVES ? H : ATT_WAVES);
-  k<<<B, threads, lds, st>>>((const bf16*)qkv, (const bf16*)out, (const bf16*)dout, lse, (bf16*)dqkv, S, H, spad,
-                             1.0f / sqrtf((float)DH));
-  return iq_launch_status();
-}
-
 constexpr size_t ATT_LDS_FWD_BUDGET = 72 * 1024;   // S=197, dh=64 (224 rows) in one stage, 2 WG/CU
 constexpr size_t ATT_LDS_BWD_BUDGET = 76 * 1024;   // S=197, dh=64: both 224-row images + statistics, 2 WG/CU
 constexpr int ATT_MAX_S = 4096;                    // lse / delta stay whole in LDS (8 B per padded row)
 
-// rows of the staged side kept in LDS at a time (multiple of 32)
-template <int DH> int bwd_chunk_rows(int S) {
-  const int spad = (S + 31) / 32 * 32;
-  const long room = (long)ATT_LDS_BWD_BUDGET - (long)2 * spad * sizeof(float);
-  int chunk = (int)(room / (2 * AttCfg<DH>::LD * 2)) / 32 * 32;
-  if (chunk > spad) chunk = spad;
-  return chunk;
+// rows of the staged side kept in LDS at a time (multiple of 32): the forward's K and V, the backward's two images
+template <int DH> constexpr int fwd_chunk_rows(int S) {
+  const int kchunk = (int)(ATT_LDS_FWD_BUDGET / (2 * AttCfg<DH>::LD * 2)) / 32 * 32;
+  return kchunk > padded32(S) ? padded32(S) : kchunk;
 }
-template <int DH> size_t bwd_lds_bytes(int S) {
-  const int spad = (S + 31) / 32 * 32;
-  return (size_t)2 * bwd_chunk_rows<DH>(S) * AttCfg<DH>::LD * 2 + (size_t)2 * spad * sizeof(float);
+template <int DH> constexpr size_t fwd_lds_bytes(int S) { return (size_t)2 * fwd_chunk_rows<DH>(S) * AttCfg<DH>::LD * 2; }
+template <int DH> constexpr int bwd_chunk_rows(int S) {
+  const long room = (long)ATT_LDS_BWD_BUDGET - (long)2 * padded32(S) * sizeof(float);
+  const int chunk = (int)(room / (2 * AttCfg<DH>::LD * 2)) / 32 * 32;
+  return chunk > padded32(S) ? padded32(S) : chunk;
+}
+template <int DH> constexpr size_t bwd_lds_bytes(int S) {
+  return (size_t)2 * bwd_chunk_rows<DH>(S) * AttCfg<DH>::LD * 2 + (size_t)2 * padded32(S) * sizeof(float);
+}
+static_assert(fwd_lds_bytes<64>(197) == 71680, "attn_fwd_kernel at S = 197, dh = 64: one stage, two workgroups per CU");
+
+// attn_bwd_once_kernel: dh = 64, no mask, padded length <= 224 rows (one chunk), 1024 threads (512 measured slower:
+// profiles/attn_bwd_once.txt).  Its LDS: the Q and dO images, lse and delta, the dS image (see the kernel).
+constexpr int ONCE_THREADS = 1024;
+static_assert(ONCE_MAX_SPAD <= 16 * (ONCE_THREADS / 64), "attn_bwd_once_kernel: its waves own one 16-key unit each");
+constexpr size_t once_lds_bytes(int S) {
+  const int spad = padded32(S), nunit = (S + 15) / 16;
+  return (size_t)2 * spad * ONCE_LD * 2 + (size_t)2 * spad * sizeof(float) + (size_t)spad * (nunit * 16 + 8) * 2;
+}
+static_assert(once_lds_bytes(197) == 155904, "attn_bwd_once_kernel at S = 197: one workgroup per CU");
+static_assert(once_lds_bytes(ONCE_MAX_SPAD) <= 160 * 1024, "attn_bwd_once_kernel: every length use_once admits fits a CU's LDS");
+inline bool use_once(int S, int dh, bool masked) { return !masked && dh == 64 && padded32(S) <= ONCE_MAX_SPAD; }
+
+template <int DH>
+int launch_frame_fwd(const void* qkv, void* out, float* lse, int B, int S, int H, hipStream_t st) {
+  const int threads = 64 * (H < ATT_WAVES ? H : ATT_WAVES);
+  return launch_lds(attn_frame_fwd_kernel<DH, (DH == 64 ? 2 : 4)>, B, threads, frame_fwd_lds(S, H, DH), st, qkv, out, lse, S, H,
+                    padded32(S), LOG2E / sqrtf((float)DH));
+}
+template <int DH>
+int launch_frame_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int B, int S, int H,
+                     hipStream_t st) {
+  const int threads = 64 * (H < ATT_WAVES ? H : ATT_WAVES);
+  return launch_lds(attn_frame_bwd_kernel<DH, (DH == 64 ? 2 : 3), (DH == 16 ? 4 : DH == 32 ? 3 : 2)>, B, threads,
+                    frame_bwd_lds(S, H, DH), st, qkv, out, dout, lse, dqkv, S, H, padded32(S), 1.0f / sqrtf((float)DH));
 }
 
 template <int DH, bool MASKED>
 int launch_fwd(const void* qkv, void* out, float* lse, const uint8_t* mask, long mask_hstride, int B, int S, int H,
                hipStream_t st) {
-  const int spad = (S + 31) / 32 * 32;
-  int kchunk = (int)(ATT_LDS_FWD_BUDGET / (2 * AttCfg<DH>::LD * 2)) / 32 * 32;
-  if (kchunk > spad) kchunk = spad;
-  const size_t lds = (size_t)2 * kchunk * AttCfg<DH>::LD * 2;
-  const float scale_log2 = LOG2E / sqrtf((float)DH);
-  if (lds > 48 * 1024)
-    (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<DH, MASKED>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  attn_fwd_kernel<DH, MASKED><<<B * H, ATT_THREADS, lds, st>>>((const bf16*)qkv, (bf16*)out, lse, mask, mask_hstride, S, H,
-                                                               kchunk, scale_log2, -10000.0f * sqrtf((float)DH));
-  return iq_launch_status();
+  return launch_lds(attn_fwd_kernel<DH, MASKED>, B * H, ATT_THREADS, fwd_lds_bytes<DH>(S), st, qkv, out, lse, mask, mask_hstride,
+                    S, H, fwd_chunk_rows<DH>(S), LOG2E / sqrtf((float)DH), -10000.0f * sqrtf((float)DH));
 }
 
 template <int DH, bool MASKED>
 int launch_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, const uint8_t* mask,
                long mask_hstride, int B, int S, int H, hipStream_t st) {
-  const int spad = (S + 31) / 32 * 32;
   const int chunk = bwd_chunk_rows<DH>(S);
   if (S > ATT_MAX_S || chunk < 32) return IQ_ERR_UNSUPPORTED;
-  const size_t lds = bwd_lds_bytes<DH>(S);
-  if (lds > 48 * 1024)
-    (void)hipFuncSetAttribute((const void*)attn_bwd_kernel<DH, MASKED>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  attn_bwd_kernel<DH, MASKED><<<B * H, ATT_THREADS, lds, st>>>((const bf16*)qkv, (const bf16*)out, (const bf16*)dout, lse,
-                                                               (bf16*)dqkv, mask, mask_hstride, S, H, spad, chunk,
-                                                               1.0f / sqrtf((float)DH), -10000.0f * sqrtf((float)DH));
-  return iq_launch_status();
+  return launch_lds(attn_bwd_kernel<DH, MASKED>, B * H, ATT_THREADS, bwd_lds_bytes<DH>(S), st, qkv, out, dout, lse, dqkv, mask,
+                    mask_hstride, S, H, padded32(S), chunk, 1.0f / sqrtf((float)DH), -10000.0f * sqrtf((float)DH));
 }
 
-// attn_bwd_once_kernel: dh = 64, no mask, padded length <= 224 rows (one chunk), 1024 threads (512 measured slower:
-// profiles/attn_bwd_once.txt).
-constexpr int ONCE_THREADS = 1024;
-static_assert(ONCE_MAX_SPAD <= 16 * (ONCE_THREADS / 64), "attn_bwd_once_kernel: its waves own one 16-key unit each");
-inline bool use_once(int S, int dh, bool masked) { return !masked && dh == 64 && (S + 31) / 32 * 32 <= ONCE_MAX_SPAD; }
 template <int NT>
 int launch_bwd_once(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int B, int S, int H,
                     hipStream_t st) {
-  const int spad = (S + 31) / 32 * 32, nunit = (S + 15) / 16;
-  const size_t lds = (size_t)2 * spad * ONCE_LD * 2 + (size_t)2 * spad * sizeof(float) + (size_t)spad * (nunit * 16 + 8) * 2;
-  auto k = attn_bwd_once_kernel<NT>;
-  if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  k<<<B * H, NT, lds, st>>>((const bf16*)qkv, (const bf16*)out, (const bf16*)dout, lse, (bf16*)dqkv, S, H, spad,
-                            1.0f / sqrtf(64.0f));
-  return iq_launch_status();
-}
-
-template <bool MASKED>
-int dispatch_fwd(const void* qkv, void* out, float* lse, const uint8_t* mask, long hs, int B, int S, int H, int dh,
-                 hipStream_t st) {
-  switch (dh) {
-    case 16: return launch_fwd<16, MASKED>(qkv, out, lse, mask, hs, B, S, H, st);
-    case 32: return launch_fwd<32, MASKED>(qkv, out, lse, mask, hs, B, S, H, st);
-    case 64: return launch_fwd<64, MASKED>(qkv, out, lse, mask, hs, B, S, H, st);
-    default: return IQ_ERR_UNSUPPORTED;
-  }
-}
-template <bool MASKED>
-int dispatch_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, const uint8_t* mask,
-                 long hs, int B, int S, int H, int dh, hipStream_t st) {
-  switch (dh) {
-    case 16: return launch_bwd<16, MASKED>(qkv, out, dout, lse, dqkv, mask, hs, B, S, H, st);
-    case 32: return launch_bwd<32, MASKED>(qkv, out, dout, lse, dqkv, mask, hs, B, S, H, st);
-    case 64: return launch_bwd<64, MASKED>(qkv, out, dout, lse, dqkv, mask, hs, B, S, H, st);
-    default: return IQ_ERR_UNSUPPORTED;
-  }
+  return launch_lds(attn_bwd_once_kernel<NT>, B * H, NT, once_lds_bytes(S), st, qkv, out, dout, lse, dqkv, S, H, padded32(S),
+                    1.0f / sqrtf(64.0f));
 }
 
 }  // namespace
@@ -1272,21 +1141,15 @@ extern "C" int iq_attn_fwd_masked(const void* qkv, void* out, float* lse, const 
   if (!iq_attn_supported(S, dh)) return IQ_ERR_UNSUPPORTED;      // before anything is recorded or launched
   hipStream_t st = (hipStream_t)stream;
   IQ_PROF(IQ_FAM_ATTN_FWD, st);
-  const bool frame = !mask && (dh == 16 || dh == 32 || dh == 64) && use_frame(S, frame_fwd_lds(S, H, dh));
+  const bool frame = !mask && use_frame(S, frame_fwd_lds(S, H, dh));
   {
     const double rows = (double)B * S, Dm = (double)H * dh;
     if (frame) IQ_PROF_K(2.0 * rows * 4.0 * Dm + 4.0 * B * H * S, 4.0 * B * H * (double)S * S * dh, "attn_frame_fwd_kernel<%d>", dh);
     else IQ_PROF_K(2.0 * rows * 4.0 * Dm + 4.0 * B * H * S, 4.0 * B * H * (double)S * S * dh, "attn_fwd_kernel<%d, %s>", dh, mask ? "true" : "false");
   }
-  if (frame) {
-    switch (dh) {
-      case 16: return launch_frame_fwd<16>(qkv, out, lse, B, S, H, st);
-      case 32: return launch_frame_fwd<32>(qkv, out, lse, B, S, H, st);
-      default: return launch_frame_fwd<64>(qkv, out, lse, B, S, H, st);
-    }
-  }
-  return mask ? dispatch_fwd<true>(qkv, out, lse, mask, mask_hstride, B, S, H, dh, st)
-              : dispatch_fwd<false>(qkv, out, lse, nullptr, 0, B, S, H, dh, st);
+  if (frame) return dispatch_dh(dh, [&](auto d) { return launch_frame_fwd<d()>(qkv, out, lse, B, S, H, st); });
+  if (mask) return dispatch_dh(dh, [&](auto d) { return launch_fwd<d(), true>(qkv, out, lse, mask, mask_hstride, B, S, H, st); });
+  return dispatch_dh(dh, [&](auto d) { return launch_fwd<d(), false>(qkv, out, lse, nullptr, 0, B, S, H, st); });
 }
 extern "C" int iq_attn_fwd(const void* qkv, void* out, float* lse, int B, int S, int H, int dh, iq_stream_t stream) {
   return iq_attn_fwd_masked(qkv, out, lse, nullptr, 0, B, S, H, dh, stream);
@@ -1301,7 +1164,7 @@ extern "C" int iq_attn_bwd_masked(const void* qkv, const void* out, const void* 
   if (!iq_attn_supported(S, dh)) return IQ_ERR_UNSUPPORTED;      // before anything is recorded or launched
   hipStream_t st = (hipStream_t)stream;
   IQ_PROF(IQ_FAM_ATTN_BWD, st);
-  const bool frame = !mask && (dh == 16 || dh == 32 || dh == 64) && use_frame(S, frame_bwd_lds(S, H, dh));
+  const bool frame = !mask && use_frame(S, frame_bwd_lds(S, H, dh));
   const bool once = !frame && use_once(S, dh, mask != nullptr);
   {
     const double rows = (double)B * S, Dm = (double)H * dh;      // qkv, out, dout read; dqkv written; 7 MFMA products
@@ -1309,16 +1172,11 @@ extern "C" int iq_attn_bwd_masked(const void* qkv, const void* out, const void* 
     else if (once) IQ_PROF_K(2.0 * rows * 8.0 * Dm + 4.0 * B * H * S, 10.0 * B * H * (double)S * S * dh, "attn_bwd_once_kernel<%d>", ONCE_THREADS);   // 5 products
     else IQ_PROF_K(2.0 * rows * 8.0 * Dm + 4.0 * B * H * S, 14.0 * B * H * (double)S * S * dh, "attn_bwd_kernel<%d, %s>", dh, mask ? "true" : "false");
   }
-  if (frame) {
-    switch (dh) {
-      case 16: return launch_frame_bwd<16>(qkv, out, dout, lse, dqkv, B, S, H, st);
-      case 32: return launch_frame_bwd<32>(qkv, out, dout, lse, dqkv, B, S, H, st);
-      default: return launch_frame_bwd<64>(qkv, out, dout, lse, dqkv, B, S, H, st);
-    }
-  }
+  if (frame) return dispatch_dh(dh, [&](auto d) { return launch_frame_bwd<d()>(qkv, out, dout, lse, dqkv, B, S, H, st); });
   if (once) return launch_bwd_once<ONCE_THREADS>(qkv, out, dout, lse, dqkv, B, S, H, st);
-  return mask ? dispatch_bwd<true>(qkv, out, dout, lse, dqkv, mask, mask_hstride, B, S, H, dh, st)
-              : dispatch_bwd<false>(qkv, out, dout, lse, dqkv, nullptr, 0, B, S, H, dh, st);
+  if (mask)
+    return dispatch_dh(dh, [&](auto d) { return launch_bwd<d(), true>(qkv, out, dout, lse, dqkv, mask, mask_hstride, B, S, H, st); });
+  return dispatch_dh(dh, [&](auto d) { return launch_bwd<d(), false>(qkv, out, dout, lse, dqkv, nullptr, 0, B, S, H, st); });
 }
 extern "C" int iq_attn_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int B,
                            int S, int H, int dh, iq_stream_t stream) {

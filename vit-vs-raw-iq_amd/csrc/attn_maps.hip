@@ -27,8 +27,8 @@
 // key are reduced by a fixed butterfly at the end.
 #include <stdint.h>
 
+#include "attn_common.h"
 #include "attn_maps.h"
-#include "common.h"
 #include "iqvit.h"
 #include "prof.h"
 
@@ -40,28 +40,11 @@ constexpr int QB = 32;                       // queries per block
 constexpr int KC = 256;                      // keys per chunk
 constexpr int KTW = KC / 16 / PM_WAVES;      // key tiles per wave
 constexpr int PLD = KC + 4;                  // fp32 row stride of the probability tile
-constexpr float LOG2E = 1.4426950408889634f;
-
-__device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
-
-template <int DH> struct PmCfg {
-  static constexpr int LD = (DH == 16) ? 16 : DH + 16;   // LDS row stride (elements), as attention.hip
-  static constexpr int KS = (DH + 31) / 32;              // 32-deep contraction steps
-  static constexpr int CPR = DH / 8;                     // 16 B chunks per row
-};
-
-template <int DH>
-__device__ __forceinline__ bf16x8 row_frag(const bf16* tile, int row, int s, int lane) {
-  const int d0 = s * 32 + 8 * (lane >> 4);
-  bf16x8 v = {};
-  if (DH >= 32 || d0 < DH) v = *reinterpret_cast<const bf16x8*>(tile + row * PmCfg<DH>::LD + d0);
-  return v;
-}
 
 // rows [r0, r0 + nrows) of a head slice (global row stride ldg) -> LDS image; rows >= S are zero
 template <int DH>
 __device__ __forceinline__ void stage(bf16* img, const bf16* base, long ldg, int r0, int nrows, int S, int tid) {
-  constexpr int CPR = PmCfg<DH>::CPR, LD = PmCfg<DH>::LD;
+  constexpr int CPR = AttCfg<DH>::CPR, LD = AttCfg<DH>::LD;
   for (int id = tid; id < nrows * CPR; id += PM_THREADS) {
     const int r = id / CPR, c = id - r * CPR;
     bf16x8 v = {};
@@ -75,13 +58,13 @@ __device__ __forceinline__ void stage(bf16* img, const bf16* base, long ldg, int
 template <int DH>
 __device__ __forceinline__ void tile_probs(const bf16* Qs, const bf16* Ks, const float lq[2], bool u1, int kc, int k0, int S,
                                            float scale_log2, int wave, int lane, f32x4 p[2][KTW]) {
-  constexpr int KS = PmCfg<DH>::KS;
+  constexpr int KS = AttCfg<DH>::KS;
   const int c16 = lane & 15, g = lane >> 4;
   bf16x8 qf[2][KS];
 #pragma unroll
   for (int u = 0; u < 2; ++u)
 #pragma unroll
-    for (int s = 0; s < KS; ++s) qf[u][s] = row_frag<DH>(Qs, u * 16 + c16, s, lane);
+    for (int s = 0; s < KS; ++s) qf[u][s] = row_frag<DH>(Qs, HeadRows<DH>{}, u * 16 + c16, s, lane);
 #pragma unroll
   for (int j = 0; j < KTW; ++j) {
     const int kt = wave + PM_WAVES * j;
@@ -90,7 +73,7 @@ __device__ __forceinline__ void tile_probs(const bf16* Qs, const bf16* Ks, const
     if (kt * 16 >= kc) continue;                 // wave-uniform
     bf16x8 kf[KS];
 #pragma unroll
-    for (int s = 0; s < KS; ++s) kf[s] = row_frag<DH>(Ks, kt * 16 + c16, s, lane);
+    for (int s = 0; s < KS; ++s) kf[s] = row_frag<DH>(Ks, HeadRows<DH>{}, kt * 16 + c16, s, lane);
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       if (u == 1 && !u1) continue;               // wave-uniform: the second half holds no query
@@ -159,13 +142,13 @@ struct ProbsArgs {
 // The raw products of this wave's tiles in the layout of tile_probs: d[u][j] = A tile (wave + 8 j) x B half u.
 template <int DH>
 __device__ __forceinline__ void tile_dots(const bf16* Bs, const bf16* As, bool u1, int kc, int wave, int lane, f32x4 d[2][KTW]) {
-  constexpr int KS = PmCfg<DH>::KS;
+  constexpr int KS = AttCfg<DH>::KS;
   const int c16 = lane & 15;
   bf16x8 bf[2][KS];
 #pragma unroll
   for (int u = 0; u < 2; ++u)
 #pragma unroll
-    for (int s = 0; s < KS; ++s) bf[u][s] = row_frag<DH>(Bs, u * 16 + c16, s, lane);
+    for (int s = 0; s < KS; ++s) bf[u][s] = row_frag<DH>(Bs, HeadRows<DH>{}, u * 16 + c16, s, lane);
 #pragma unroll
   for (int j = 0; j < KTW; ++j) {
     const int kt = wave + PM_WAVES * j;
@@ -174,7 +157,7 @@ __device__ __forceinline__ void tile_dots(const bf16* Bs, const bf16* As, bool u
     if (kt * 16 >= kc) continue;
     bf16x8 af[KS];
 #pragma unroll
-    for (int s = 0; s < KS; ++s) af[s] = row_frag<DH>(As, kt * 16 + c16, s, lane);
+    for (int s = 0; s < KS; ++s) af[s] = row_frag<DH>(As, HeadRows<DH>{}, kt * 16 + c16, s, lane);
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       if (u == 1 && !u1) continue;
@@ -188,7 +171,7 @@ __device__ __forceinline__ void tile_dots(const bf16* Bs, const bf16* As, bool u
 // the dO block and the V chunk are staged where Q and K were and dP is formed in the same layout.
 template <int DH, bool GRAD>
 __device__ __forceinline__ void probs_body(const ProbsArgs& a) {
-  using Cf = PmCfg<DH>;
+  using Cf = AttCfg<DH>;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   bf16* Qs = reinterpret_cast<bf16*>(smem);
   bf16* Ks = Qs + QB * Cf::LD;
@@ -301,7 +284,7 @@ struct RolloutArgs {
 
 template <int DH>
 __global__ __launch_bounds__(PM_THREADS) void attn_rollout_kernel(RolloutArgs a) {
-  using Cf = PmCfg<DH>;
+  using Cf = AttCfg<DH>;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   bf16* Qs = reinterpret_cast<bf16*>(smem);
   bf16* Ks = Qs + QB * Cf::LD;
@@ -374,7 +357,7 @@ struct StepArgs {
 
 template <int DH>
 __global__ __launch_bounds__(PM_THREADS) void attn_relevance_step_kernel(StepArgs a) {
-  using Cf = PmCfg<DH>;
+  using Cf = AttCfg<DH>;
   constexpr int KS = Cf::KS;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   bf16* Ks = reinterpret_cast<bf16*>(smem);
@@ -408,8 +391,8 @@ __global__ __launch_bounds__(PM_THREADS) void attn_relevance_step_kernel(StepArg
         if (q0 == 0) {
 #pragma unroll
           for (int s = 0; s < KS; ++s) {
-            kf[s] = row_frag<DH>(Ks, wave * 16 + c16, s, lane);
-            vf[s] = row_frag<DH>(Vs, wave * 16 + c16, s, lane);
+            kf[s] = row_frag<DH>(Ks, HeadRows<DH>{}, wave * 16 + c16, s, lane);
+            vf[s] = row_frag<DH>(Vs, HeadRows<DH>{}, wave * 16 + c16, s, lane);
           }
         }
 #pragma unroll
@@ -422,8 +405,8 @@ __global__ __launch_bounds__(PM_THREADS) void attn_relevance_step_kernel(StepArg
           f32x4 sc = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
           for (int s = 0; s < KS; ++s) {
-            const bf16x8 qf = row_frag<DH>(Qs, u * 16 + c16, s, lane);
-            const bf16x8 df = row_frag<DH>(Ds, u * 16 + c16, s, lane);
+            const bf16x8 qf = row_frag<DH>(Qs, HeadRows<DH>{}, u * 16 + c16, s, lane);
+            const bf16x8 df = row_frag<DH>(Ds, HeadRows<DH>{}, u * 16 + c16, s, lane);
             sc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[s], qf, sc, 0, 0, 0);
             dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf[s], df, dp, 0, 0, 0);
           }
@@ -455,11 +438,12 @@ __global__ __launch_bounds__(PM_THREADS) void attn_relevance_step_kernel(StepArg
   }
 }
 
-template <int DH> size_t probs_lds() { return (size_t)QB * PmCfg<DH>::LD * 2 + (size_t)KC * PmCfg<DH>::LD * 2 + (size_t)QB * PLD * 4; }
+template <int DH> constexpr size_t probs_lds() {
+  return (size_t)QB * AttCfg<DH>::LD * 2 + (size_t)KC * AttCfg<DH>::LD * 2 + (size_t)QB * PLD * 4;
+}
 
 template <int DH, bool GRAD>
 int launch_probs(const ProbsArgs& a, int B, hipStream_t st) {
-  const size_t lds = probs_lds<DH>();
   // per frame where the forward runs its per-frame kernel (short sequences); else per (frame, head, query block), with the
   // groups a fixed-order mean needs kept inside one workgroup
   const bool frame = a.S <= 128;
@@ -473,30 +457,18 @@ int launch_probs(const ProbsArgs& a, int B, hipStream_t st) {
     g.nqg = 1;
   }
   const unsigned grid = (unsigned)((long)B * g.nhg * g.nqg);
-  if (GRAD) {
-    (void)hipFuncSetAttribute((const void*)attn_grad_probs_kernel<DH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attn_grad_probs_kernel<DH><<<grid, PM_THREADS, lds, st>>>(g);
-  } else {
-    (void)hipFuncSetAttribute((const void*)attn_probs_kernel<DH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attn_probs_kernel<DH><<<grid, PM_THREADS, lds, st>>>(g);
-  }
-  return iq_launch_status();
+  return launch_lds(GRAD ? attn_grad_probs_kernel<DH> : attn_probs_kernel<DH>, grid, PM_THREADS, probs_lds<DH>(), st, g);
 }
 
 template <int DH>
 int launch_step(const StepArgs& a, int B, hipStream_t st) {
-  const size_t lds = (size_t)(2 * RKB + 2 * RQC) * PmCfg<DH>::LD * 2;
-  (void)hipFuncSetAttribute((const void*)attn_relevance_step_kernel<DH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  attn_relevance_step_kernel<DH><<<(unsigned)((long)B * a.nkb), PM_THREADS, lds, st>>>(a);
-  return iq_launch_status();
+  return launch_lds(attn_relevance_step_kernel<DH>, (unsigned)((long)B * a.nkb), PM_THREADS,
+                    (size_t)(2 * RKB + 2 * RQC) * AttCfg<DH>::LD * 2, st, a);
 }
 
 template <int DH>
 int launch_rollout(const RolloutArgs& a, int B, hipStream_t st) {
-  const size_t lds = probs_lds<DH>() + (size_t)2 * ((a.S + QB - 1) / QB * QB) * 4;
-  (void)hipFuncSetAttribute((const void*)attn_rollout_kernel<DH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  attn_rollout_kernel<DH><<<B, PM_THREADS, lds, st>>>(a);
-  return iq_launch_status();
+  return launch_lds(attn_rollout_kernel<DH>, B, PM_THREADS, probs_lds<DH>() + (size_t)2 * padded32(a.S) * 4, st, a);
 }
 
 }  // namespace
@@ -520,11 +492,7 @@ extern "C" int iq_attn_probs(const void* qkv, const float* lse, float* out, long
   a.S = S; a.H = H; a.rows = rows; a.heads = heads; a.nhg = 1; a.nqg = 1;
   a.scale_log2 = LOG2E / sqrtf((float)dh);
   a.dout = nullptr; a.positive = 0;
-  switch (dh) {
-    case 16: return launch_probs<16, false>(a, B, st);
-    case 32: return launch_probs<32, false>(a, B, st);
-    default: return launch_probs<64, false>(a, B, st);
-  }
+  return dispatch_dh(dh, [&](auto d) { return launch_probs<d(), false>(a, B, st); });
 }
 
 extern "C" int iq_attn_grad_probs(const void* qkv, const float* lse, const void* dout, float* out, long out_bstride, int B, int S,
@@ -547,11 +515,7 @@ extern "C" int iq_attn_grad_probs(const void* qkv, const float* lse, const void*
   a.S = S; a.H = H; a.rows = rows; a.heads = heads; a.nhg = 1; a.nqg = 1;
   a.scale_log2 = LOG2E / sqrtf((float)dh);
   a.dout = (const bf16*)dout; a.positive = positive;
-  switch (dh) {
-    case 16: return launch_probs<16, true>(a, B, st);
-    case 32: return launch_probs<32, true>(a, B, st);
-    default: return launch_probs<64, true>(a, B, st);
-  }
+  return dispatch_dh(dh, [&](auto d) { return launch_probs<d(), true>(a, B, st); });
 }
 
 int attn_relevance_step_launch(const void* qkv, const float* lse, const void* dout, const float* r_in, float* r_out, int B, int S,
@@ -568,11 +532,7 @@ int attn_relevance_step_launch(const void* qkv, const float* lse, const void* do
   a.qkv = (const bf16*)qkv; a.lse = lse; a.dout = (const bf16*)dout; a.rin = r_in; a.rout = r_out;
   a.S = S; a.H = H; a.nkb = (S + RKB - 1) / RKB; a.start = start;
   a.scale_log2 = LOG2E / sqrtf((float)dh);
-  switch (dh) {
-    case 16: return launch_step<16>(a, B, st);
-    case 32: return launch_step<32>(a, B, st);
-    default: return launch_step<64>(a, B, st);
-  }
+  return dispatch_dh(dh, [&](auto d) { return launch_step<d()>(a, B, st); });
 }
 
 extern "C" int iq_attn_relevance_step(const void* qkv, const float* lse, const void* dout, const float* r_in, float* r_out, int B,
@@ -598,9 +558,5 @@ int attn_rollout_launch(const unsigned char* qkv0, long qkv_lstride, const unsig
   RolloutArgs a;
   a.qkv0 = qkv0; a.qkv_lstride = qkv_lstride; a.lse0 = lse0; a.lse_lstride = lse_lstride; a.out = out;
   a.L = L; a.S = S; a.H = H; a.cls = cls; a.alpha = alpha; a.scale_log2 = LOG2E / sqrtf((float)dh);
-  switch (dh) {
-    case 16: return launch_rollout<16>(a, B, st);
-    case 32: return launch_rollout<32>(a, B, st);
-    default: return launch_rollout<64>(a, B, st);
-  }
+  return dispatch_dh(dh, [&](auto d) { return launch_rollout<d()>(a, B, st); });
 }
