@@ -587,6 +587,58 @@ int iq_frames_cyclic(const float* x /*[n,2,len]*/, const float* table /*DEVICE [
                      float* out /*[n,C,n_fft,n_fft]*/, int n_frames, int len, const iq_cyclic_t* par, iq_stream_t stream);
 int iq_frames_cyclic_bwd(const float* x, const float* table, const float* rot, const float* dout /*[n,C,n_fft,n_fft]*/,
                          float* dx /*[n,2,len]*/, int n_frames, int len, const iq_cyclic_t* par, iq_stream_t stream);
+/* Constellation front end (csrc/constellation.hip): the smoothed 2-D density of the (I, Q) points of a frame as an image, and
+ * its adjoint.  x[n_frames, 2, len] planar fp32 as above (for symbols: the transposed output of iq_frames_receive).  table is
+ * DEVICE fp32 [radius * n_frac + 1], plain numbers to the kernel: a radial profile sampled every 1 / n_frac pixel of distance;
+ * the caller makes table[last] = 0 for continuity.  Column weight of point n for image column c = 0 .. width-1:
+ *   u = fmaf(I[n], x_scale, x_off)      pixel units; pixel c covers [c, c+1), its centre is c + 0.5
+ *   e = u - (c + 0.5f),  d = |e|,  t = d * (float)n_frac   (one rounding)
+ *   not (t < radius * n_frac): b[n,c] = 0 exactly (a NaN or infinite sample fails the compare: it contributes to no pixel)
+ *   else i = (int)floorf(t), f = t - i (exact), b[n,c] = fmaf(f, table[i+1] - table[i], table[i]), the difference rounded first.
+ * The row weight a[n,r], r = 0 .. height-1, is the same from Q[n] with y_scale / y_off.  D[r,c] = the fp32 fmaf chain over n
+ * ascending of a[n,r] * b[n,c], starting from +0 (fp32-input MFMA).  Skipping any n whose a[n,r] or b[n,c] is zero leaves this
+ * chain unchanged bit for bit because the table is finite, and the kernel skips the points that cannot reach a 32 x 32 tile;
+ * non-finite table entries make the result unspecified.  v = D * inv_norm; mode 0: out = v * scale + shift; mode 1: out =
+ * log10f(v + floor) * scale + shift, the product and the sum rounded separately.  out[n_frames, 1, height, width]: row 0 is the
+ * most negative Q, column c is contiguous.  No atomics: two runs agree bit for bit, and a frame's image depends on neither
+ * n_frames nor its position.  Nothing is allocated, the host is not synchronised.
+ * Launch shape (the image is the same bit for bit whatever it is): one workgroup per (frame, 32 image rows); its four waves take
+ * the 32-column tiles in turn, each compacting the frame's points within reach of its tile (order preserved) and running the
+ * chain over those only.  LDS: the frame, the table and four lists of up to len + 7 16-bit indices, at most 132.1 KB of 160 KB.
+ * iq_frames_constellation_bwd: dx[n_frames, 2, len] = the gradient of sum(out * dout) with respect to x; everything is
+ * recomputed from x (no workspace), nothing but dx is written.  g[r,c] = (dout * scale) * inv_norm; in mode 1 divided by
+ * ln 10 * (v + floor), v the forward's value bit for bit.  b'[n,c] = sgn(e) * (table[i+1] - table[i]) where the compare above
+ * passes (the slope of the segment i = floor(t) the weight was taken from, also where the weight itself happens to be 0) and 0
+ * elsewhere, sgn(0) = 0; a' likewise for rows.
+ *   dx[.,0,n] = (x_scale * n_frac) * sum_{r,c} g[r,c] a[n,r]  b'[n,c]
+ *   dx[.,1,n] = (y_scale * n_frac) * sum_{r,c} g[r,c] a'[n,r] b[n,c]
+ * Order of the sums: the 32 x 32 tiles in row-major order; per tile the rows r ascending; per row s = the fmaf chain over the
+ * tile's columns c ascending of g[r,c] * b'[n,c] (resp. b[n,c]) from +0, then sum = fmaf(a[n,r], s, sum) (resp. a'[n,r]); rows
+ * and columns out of the point's reach and rows with a = a' = 0 are skipped; one product by the rounded (x_scale * n_frac) at
+ * the end.  Element n of dx is read and written by one thread only (n mod 256 of the frame's workgroup), in program order: no
+ * atomics, two runs agree bit for bit, a frame's gradient depends on neither n_frames nor its position.  A dropped sample
+ * (NaN, infinite, or out of reach of every pixel) gets exactly 0.  One workgroup per frame; LDS: the frame, the table, four
+ * 32 x 33 tiles of g and the four lists, at most 148.6 KB of 160 KB, so the adjoint refuses nothing the forward takes.
+ * IQ_STATUS_ARG before any launch, outputs untouched: NULL x / table / out / dout / dx / par, len < 1, mode outside {0,1}, a
+ * non-finite x_scale / x_off / y_scale / y_off / inv_norm / floor / scale / shift, floor <= 0 in mode 1, x / table / out /
+ * dout / dx not 4-byte aligned (the kernels move single floats; 16-byte aligned frames of even len are staged in 16-byte
+ * groups).  IQ_STATUS_UNSUPPORTED before any launch: height or width not a multiple of 32 in [32, 256]; radius outside
+ * 1..16; n_frac outside 1..64; len * 8 bytes above 64 KB (one workgroup keeps one frame in LDS).  n_frames <= 0: success,
+ * nothing is launched. */
+typedef struct iq_constellation {
+  int height, width;   /* image rows (Q) and columns (I): multiples of 32 in [32, 256] */
+  int radius;          /* pixels, 1 .. 16: a point reaches at most two tiles per axis */
+  int n_frac;          /* table samples per pixel, 1 .. 64 */
+  int mode;            /* 0: out = v*scale + shift;  1: out = log10(v + floor)*scale + shift */
+  float x_scale, x_off, y_scale, y_off;   /* pixel coordinate = sample * scale + off */
+  float inv_norm, floor, scale, shift;    /* v = D * inv_norm */
+} iq_constellation_t;
+int iq_frames_constellation(const float* x /*[n,2,len]*/, const float* table /*DEVICE [radius*n_frac+1]*/,
+                            float* out /*[n,1,height,width]*/, int n_frames, int len, const iq_constellation_t* par,
+                            iq_stream_t stream);
+int iq_frames_constellation_bwd(const float* x, const float* table, const float* dout /*[n,1,height,width]*/,
+                                float* dx /*[n,2,len]*/, int n_frames, int len, const iq_constellation_t* par,
+                                iq_stream_t stream);
 int iq_patchify(const float* src, void* patches, int kind, int B, int C, int H, int W, int p, int Kpad,
                 iq_stream_t stream);
 int iq_cls_rows(const float* cls, const float* pe, void* x0, int B, int S, int D, const iq_dropout_t* drop,

@@ -17,6 +17,7 @@ Import name: `vit_vs_raw_iq_amd` (the directory name contains hyphens; the repo-
   spectrogram -- spectrogram front end on the device: (B, 2, len) frames -> the (B, 1, n_fft, width) image of the ViT, differentiable
   cyclic    -- cyclic-spectrum front end on the device: (B, 2, len) frames -> the (B, C, n_fft, n_fft) spectral correlation image,
                differentiable on request
+  constellation -- constellation front end on the device: (B, 2, len) points -> the (B, 1, height, width) density image, differentiable
   receiver  -- receiver on the device: matched filter, timing estimate, one sample per symbol, differentiable (Receiver, ReceivedSynth)
   _native   -- ctypes binding of include/iqvit.h  (libiqvit.so; no fallback)
   ViT.models.amc_transformer / transformer_rawIQ.models.transformer_rawIQ
@@ -35,6 +36,7 @@ from .synth import FrameSynth, SynthStream, synth_reference, train_on_stream
 from .waveform import ShapedSynth, gmsk_table, rrc_table, waveform_reference
 from .spectrogram import Spectrogram, spectrogram_reference, spectrogram_reference_bwd
 from .cyclic import CyclicSpectrum, cyclic_reference, cyclic_reference_bwd
+from .constellation import Constellation, constellation_reference, constellation_reference_bwd
 from .receiver import (Receiver, ReceivedSynth, mf_table, receiver_reference, receiver_reference_bwd,
                        transmitted_index)
 
@@ -45,4 +47,5 @@ __all__ = ["AMCTransformerViT", "AMCTransformerRawIQ", "EncoderViT", "EncoderRaw
            "pgd", "robustness_curve", "Impairments", "impair", "impair_reference", "impairment_curve", "FrameSynth",
            "SynthStream", "synth_reference", "train_on_stream", "Spectrogram", "spectrogram_reference", "spectrogram_reference_bwd",
            "ShapedSynth", "rrc_table", "gmsk_table", "waveform_reference", "Receiver", "ReceivedSynth", "mf_table", "receiver_reference",
-           "receiver_reference_bwd", "transmitted_index", "CyclicSpectrum", "cyclic_reference", "cyclic_reference_bwd"]
+           "receiver_reference_bwd", "transmitted_index", "CyclicSpectrum", "cyclic_reference", "cyclic_reference_bwd",
+           "Constellation", "constellation_reference", "constellation_reference_bwd"]

@@ -60,6 +60,12 @@ class Spectrogram(C.Structure):
                 ("inv_norm", C.c_float), ("floor", C.c_float), ("scale", C.c_float), ("shift", C.c_float)]
 
 
+class Constellation(C.Structure):
+    _fields_ = [("height", C.c_int), ("width", C.c_int), ("radius", C.c_int), ("n_frac", C.c_int), ("mode", C.c_int),
+                ("x_scale", C.c_float), ("x_off", C.c_float), ("y_scale", C.c_float), ("y_off", C.c_float),
+                ("inv_norm", C.c_float), ("floor", C.c_float), ("scale", C.c_float), ("shift", C.c_float)]
+
+
 class Cyclic(C.Structure):
     _fields_ = [("n_fft", C.c_int), ("hop", C.c_int), ("pad", C.c_int), ("columns", C.c_int), ("kind", C.c_int),
                 ("mode", C.c_int), ("inv_norm", C.c_float), ("floor", C.c_float), ("scale", C.c_float), ("shift", C.c_float)]
@@ -151,6 +157,8 @@ SIGNATURES = {
     "iq_frames_spectrogram_bwd": (_I, [_P, _P, _P, _P, _I, _I, C.POINTER(Spectrogram), _P]),
     "iq_frames_cyclic": (_I, [_P, _P, _P, _P, _I, _I, C.POINTER(Cyclic), _P]),
     "iq_frames_cyclic_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, C.POINTER(Cyclic), _P]),
+    "iq_frames_constellation": (_I, [_P, _P, _P, _I, _I, C.POINTER(Constellation), _P]),
+    "iq_frames_constellation_bwd": (_I, [_P, _P, _P, _P, _I, _I, C.POINTER(Constellation), _P]),
     "iq_patchify": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "iq_cls_rows": (_I, [_P, _P, _P, _I, _I, _I, C.POINTER(Dropout), _P]),
     "iq_embed_bwd_gather": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, C.POINTER(Dropout), _I, _P]),

@@ -151,14 +151,16 @@ def _take(layout, length, h, w):
 
 
 def _front_end(spectrogram, layout, length):
-    """The `spectrogram=` argument of an input path: None, or a spectrogram.Spectrogram or cyclic.CyclicSpectrum for frames of
-    `length` samples, which needs layout 'vit' (the launch in front of it then runs with take = len and the image is (B, 1,
-    n_fft, width), for a CyclicSpectrum (B, channels, n_fft, n_fft))."""
+    """The `spectrogram=` argument of an input path: None, or a spectrogram.Spectrogram, cyclic.CyclicSpectrum or
+    constellation.Constellation for frames of `length` samples, which needs layout 'vit' (the launch in front of it then runs
+    with take = len and the image is (B, 1, n_fft, width), for a CyclicSpectrum (B, channels, n_fft, n_fft), for a Constellation
+    (B, 1, height, width))."""
     if spectrogram is None:
         return None
+    from .constellation import Constellation
     from .cyclic import CyclicSpectrum
     from .spectrogram import Spectrogram
-    if not isinstance(spectrogram, (Spectrogram, CyclicSpectrum)):
+    if not isinstance(spectrogram, (Spectrogram, CyclicSpectrum, Constellation)):
         raise TypeError(f"spectrogram must be a Spectrogram or None, got {type(spectrogram).__name__}")
     if layout != "vit":
         raise ValueError(f"a spectrogram is an image: layout must be 'vit', got {layout!r}")
