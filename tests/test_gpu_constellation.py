@@ -28,81 +28,24 @@ import pytest
 import torch
 
 import constellation_ref as R
+from frontend_gpu import GUARD, SENTINEL, abi_call, bits, dev, on_device, same_bits, small_vit
 from prof_names import kernel_launches
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 64                     # floats in front of and behind every buffer (256 bytes: keeps the 16-byte alignment)
-SENTINEL = -12345.5
-
-
-def dev():
-    return torch.device("cuda:0")
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.int32)
-
-
-def guarded(a, fill):
-    """A copy of `a` on the device between two guards of `fill` -> (whole buffer, the part that holds a)."""
-    a = np.ascontiguousarray(a, dtype=np.float32)
-    buf = torch.full((a.size + 2 * GUARD,), fill, dtype=torch.float32, device=dev())
-    buf[GUARD:GUARD + a.size] = torch.from_numpy(a.reshape(-1)).to(dev())
-    return buf, buf[GUARD:GUARD + a.size]
-
-
-def guards_intact(buf, fill):
-    g = torch.cat([buf[:GUARD], buf[-GUARD:]]).cpu().numpy()
-    return bool(np.all(np.isnan(g))) if np.isnan(fill) else bool(np.all(g == np.float32(fill)))
-
-
 def abi_forward(x, table, par, expect_kernel=True):
     """x (n, 2, len), table numpy -> image (n, 1, height, width) numpy through the C ABI.  x and the table lie between NaN guards
     (a read outside either poisons the image: a NaN weight reaches every pixel of its tile), the image between sentinels."""
-    import vit_vs_raw_iq_amd._native as N
-    L = N.lib()
     n, _, length = x.shape
-    xb, xv = guarded(x, np.nan)
-    tb, tv = guarded(table, np.nan)
-    ob, ov = guarded(np.full((n, 1, par.height, par.width), SENTINEL), SENTINEL)
-
-    def run():
-        N.check(L.iq_frames_constellation(xv.data_ptr(), tv.data_ptr(), ov.data_ptr(), n, length, ctypes.byref(par),
-                                          N.stream_handle()), "iq_frames_constellation")
-    if expect_kernel:
-        assert kernel_launches(L, run) == {"constellation_fwd_kernel": 1}
-    else:
-        run()
-    torch.cuda.synchronize()
-    assert guards_intact(ob, SENTINEL) and guards_intact(xb, np.nan) and guards_intact(tb, np.nan)
-    return ov.cpu().numpy().reshape(n, 1, par.height, par.width)
+    return abi_call("iq_frames_constellation", "constellation_fwd_kernel", (x, table), (n, 1, par.height, par.width), n, length,
+                    par, expect_kernel)
 
 
 def abi_backward(x, table, dout, par, expect_kernel=True):
     """-> dx (n, 2, len) numpy through the C ABI; dx lies between sentinels and is pre-filled with the sentinel."""
-    import vit_vs_raw_iq_amd._native as N
-    L = N.lib()
     n, _, length = x.shape
-    xb, xv = guarded(x, np.nan)
-    tb, tv = guarded(table, np.nan)
-    db, dv = guarded(dout, np.nan)
-    gb, gv = guarded(np.full((n, 2, length), SENTINEL), SENTINEL)
-
-    def run():
-        N.check(L.iq_frames_constellation_bwd(xv.data_ptr(), tv.data_ptr(), dv.data_ptr(), gv.data_ptr(), n, length,
-                                              ctypes.byref(par), N.stream_handle()), "iq_frames_constellation_bwd")
-    if expect_kernel:
-        assert kernel_launches(L, run) == {"constellation_bwd_kernel": 1}
-    else:
-        run()
-    torch.cuda.synchronize()
-    assert guards_intact(gb, SENTINEL) and guards_intact(db, np.nan) and guards_intact(xb, np.nan) and guards_intact(tb, np.nan)
-    return gv.cpu().numpy().reshape(n, 2, length)
-
-
-def on_device(x):
-    return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(dev())
+    return abi_call("iq_frames_constellation_bwd", "constellation_bwd_kernel", (x, table, dout), (n, 2, length), n, length, par,
+                    expect_kernel)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -275,18 +218,11 @@ def test_log_constellation_and_its_gradient_against_the_fp64_definition(name):
 # ---------------------------------------------------------------------------------------------------------------------------
 # 4. through Python, 5. independence
 # ---------------------------------------------------------------------------------------------------------------------------
-def small_vit(h=32, w=64):
-    import vit_vs_raw_iq_amd as P
-    torch.manual_seed(3)
-    return P.AMCTransformerViT(in_channels=1, img_size_h=h, img_size_w=w, patch_size=16, num_classes=4, d_model=128, n_head=8,
-                               n_layers=2, ffn_hidden=512, drop_prob=0.0, device="cuda").to(dev()).eval()
-
-
 @pytest.mark.parametrize("mode", ["power", "log"])
 def test_x_grad_through_a_vit_equals_the_chained_abi_calls(mode):
     import vit_vs_raw_iq_amd._native as N
     from vit_vs_raw_iq_amd import Constellation
-    m = small_vit()
+    m = small_vit(1, 32, 64)
     con = Constellation.for_model(m, 128, mode=mode, scale=50.0 if mode == "power" else 1.0)
     assert (con.height, con.width) == (32, 64)
     x0 = zscored_frames((0, 1, 2, 4, 7), 128)
@@ -424,10 +360,6 @@ def test_refusals_leave_the_outputs_untouched():
 STATS = {"i_mean": 0.01, "i_std": 0.9, "q_mean": -0.02, "q_std": 1.1}
 
 
-def same_bits(a, b):
-    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
-
-
 def direct(raw, layout, h, w, imp=None, seed=0, step=0, frame_base=0):
     """The parent's output: iq_frames_preprocess / iq_frames_impair called directly."""
     import vit_vs_raw_iq_amd._native as N
@@ -481,7 +413,7 @@ def test_a_vit_trains_on_constellations_of_received_symbols_and_the_curve_runs()
     rs = ReceivedSynth(ws, Receiver.for_synth(ws))
     assert rs.length == 128
     stats = rs.stats(n_subset=64)
-    m = small_vit().train()
+    m = small_vit(1, 32, 64).train()
     con = Constellation.for_model(m, rs.length)
     sym, y, _ = rs.generate(64, 0, 1)
     x = impair(sym, stats, "rawiq", Impairments())

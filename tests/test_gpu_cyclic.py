@@ -25,34 +25,12 @@ import pytest
 import torch
 
 import cyclic_ref as R
+from frontend_gpu import GUARD, SENTINEL, abi_call, bits, dev, on_device, same_bits, small_vit
 from prof_names import kernel_launches
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 64                     # floats in front of and behind every buffer (256 bytes: keeps the 16-byte alignment)
-SENTINEL = -12345.5
 KINDS = ("scf", "conj", "both")
-
-
-def dev():
-    return torch.device("cuda:0")
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.int32)
-
-
-def guarded(a, fill):
-    """A copy of `a` on the device between two guards of `fill` -> (whole buffer, the part that holds a)."""
-    a = np.ascontiguousarray(a, dtype=np.float32)
-    buf = torch.full((a.size + 2 * GUARD,), fill, dtype=torch.float32, device=dev())
-    buf[GUARD:GUARD + a.size] = torch.from_numpy(a.reshape(-1)).to(dev())
-    return buf, buf[GUARD:GUARD + a.size]
-
-
-def guards_intact(buf, fill):
-    g = torch.cat([buf[:GUARD], buf[-GUARD:]]).cpu().numpy()
-    return bool(np.all(np.isnan(g))) if np.isnan(fill) else bool(np.all(g == np.float32(fill)))
 
 
 def struct(n_fft, columns, hop, pad, kind=2, mode=0, inv_norm=1.0, floor=1.0, scale=1.0, shift=0.0):
@@ -78,25 +56,9 @@ def abi_forward(x, table, rot, par, expect_kernel=True):
     """x (n, 2, len), table (2, n_fft, n_fft), rot (2, n_fft) numpy -> image (n, C, n_fft, n_fft) numpy through the C ABI.  x and
     both tables lie between NaN guards (a read outside any of them poisons the image), the image between sentinels and is
     pre-filled with the sentinel (an element the kernel does not write shows)."""
-    import vit_vs_raw_iq_amd._native as N
-    L = N.lib()
     n, _, length = x.shape
-    C = 2 if par.kind == 2 else 1
-    xb, xv = guarded(x, np.nan)
-    tb, tv = guarded(table, np.nan)
-    rb, rv = guarded(rot, np.nan)
-    ob, ov = guarded(np.full((n, C, par.n_fft, par.n_fft), SENTINEL), SENTINEL)
-
-    def run():
-        N.check(L.iq_frames_cyclic(xv.data_ptr(), tv.data_ptr(), rv.data_ptr(), ov.data_ptr(), n, length, ctypes.byref(par),
-                                   N.stream_handle()), "iq_frames_cyclic")
-    if expect_kernel:
-        assert kernel_launches(L, run) == {kernel_name(par, length): 1}
-    else:
-        run()
-    torch.cuda.synchronize()
-    assert guards_intact(ob, SENTINEL) and guards_intact(xb, np.nan) and guards_intact(tb, np.nan) and guards_intact(rb, np.nan)
-    return ov.cpu().numpy().reshape(n, C, par.n_fft, par.n_fft)
+    return abi_call("iq_frames_cyclic", kernel_name(par, length), (x, table, rot), (n, 2 if par.kind == 2 else 1, par.n_fft, par.n_fft),
+                    n, length, par, expect_kernel)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -165,10 +127,6 @@ def test_an_offset_frame_pointer_takes_the_scalar_staging_path():
 # ---------------------------------------------------------------------------------------------------------------------------
 # 2. real tables against fp64
 # ---------------------------------------------------------------------------------------------------------------------------
-def on_device(x):
-    return torch.from_numpy(np.array(x, dtype=np.float32)).to(dev())                  # a copy: zscored_frames() is read-only
-
-
 @functools.lru_cache(maxsize=None)
 def zscored_frames():
     """Frames of a FrameSynth stream (one sample per symbol) and of a ShapedSynth stream (RRC, 8 samples per symbol), each BPSK /
@@ -268,10 +226,6 @@ def test_both_is_scf_and_conj_stacked_bit_for_bit(mode):
 # ---------------------------------------------------------------------------------------------------------------------------
 # 4. independence and isolation
 # ---------------------------------------------------------------------------------------------------------------------------
-def same_bits(a, b):
-    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
-
-
 @pytest.mark.parametrize("mode", ["log", "coherence"])
 def test_a_frame_does_not_depend_on_the_call_it_is_part_of(mode):
     from vit_vs_raw_iq_amd import CyclicSpectrum
@@ -341,13 +295,6 @@ def test_graph_replay_equals_eager():
     assert same_bits(held, eager_b) and not same_bits(eager_a, eager_b)
 
 
-def small_vit(in_channels=2, h=64, w=64):
-    import vit_vs_raw_iq_amd as P
-    torch.manual_seed(3)
-    return P.AMCTransformerViT(in_channels=in_channels, img_size_h=h, img_size_w=w, patch_size=16, num_classes=4, d_model=128,
-                               n_head=8, n_layers=2, ffn_hidden=512, drop_prob=0.0, device="cuda").to(dev()).eval()
-
-
 def test_a_two_channel_vit_trains_on_cyclic_images_of_fresh_frames_and_the_curve_runs():
     """BPSK / QPSK / GMSK / OQPSK at 4 samples per symbol and 20 dB: the classes differ in exactly what the two channels show.
     Twelve steps of 32 never-repeated frames; the mean loss of the last four steps is below that of the first four."""
@@ -355,7 +302,7 @@ def test_a_two_channel_vit_trains_on_cyclic_images_of_fresh_frames_and_the_curve
     from vit_vs_raw_iq_amd.trainer import FusedTrainer
     ws = ShapedSynth(["BPSK", "QPSK", "GMSK", "OQPSK"], snrs_db=(20.0,), length=1024, seed=11, sps=4, device=dev())
     stats = ws.stats(64)
-    m = small_vit().train()
+    m = small_vit(2, 64, 64).train()
     cs = CyclicSpectrum.for_model(m, 1024)
     assert (cs.n_fft, cs.kind, cs.channels, cs.mode) == (64, "both", 2, "coherence")
     raw, y, _ = ws.generate(64, 0, 1)

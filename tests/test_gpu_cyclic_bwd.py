@@ -24,8 +24,9 @@ import torch
 
 import cyclic_bwd_ref as A
 import cyclic_ref as R
+from frontend_gpu import GUARD, SENTINEL, abi_call, bits, dev, on_device, same_bits, small_vit
 from prof_names import kernel_launches
-from test_gpu_cyclic import GUARD, SENTINEL, bits, dev, guarded, guards_intact, on_device, same_bits, small_vit, struct, zscored_frames
+from test_gpu_cyclic import struct, zscored_frames
 
 pytestmark = pytest.mark.gpu
 
@@ -51,28 +52,9 @@ def abi_backward(x, table, rot, dout, par, expect_kernel=True):
     """x (n, 2, len), table, rot, dout (n, C, n_fft, n_fft) numpy -> dx (n, 2, len) numpy through the C ABI.  The four operands lie
     between NaN guards (a read outside any of them poisons dx), dx between sentinels and is pre-filled with the sentinel (an
     element the kernel does not write shows)."""
-    import vit_vs_raw_iq_amd._native as N
-    L = N.lib()
     n, _, length = x.shape
-    xb, xv = guarded(x, np.nan)
-    tb, tv = guarded(table, np.nan)
-    rb, rv = guarded(rot, np.nan)
-    db, dv = guarded(dout, np.nan)
-    ob, ov = guarded(np.full((n, 2, length), SENTINEL), SENTINEL)
-
-    def run():
-        N.check(L.iq_frames_cyclic_bwd(xv.data_ptr(), tv.data_ptr(), rv.data_ptr(), dv.data_ptr(), ov.data_ptr(), n, length,
-                                       ctypes.byref(par), N.stream_handle()), "iq_frames_cyclic_bwd")
-    if expect_kernel:
-        assert kernel_launches(L, run) == {kernel_name(par, length): 1}
-    else:
-        run()
-    torch.cuda.synchronize()
-    assert guards_intact(ob, SENTINEL)
-    assert guards_intact(xb, np.nan) and guards_intact(tb, np.nan) and guards_intact(rb, np.nan) and guards_intact(db, np.nan)
-    # nothing but dx is written: the operands still hold what they held
-    assert np.array_equal(bits(xv.cpu().numpy()), bits(x).reshape(-1)) and np.array_equal(bits(dv.cpu().numpy()), bits(dout).reshape(-1))
-    return ov.cpu().numpy().reshape(n, 2, length)
+    return abi_call("iq_frames_cyclic_bwd", kernel_name(par, length), (x, table, rot, dout), (n, 2, length), n, length, par,
+                    expect_kernel)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -154,7 +136,7 @@ def test_x_grad_against_the_fp64_adjoint(name, mode):
 def test_x_grad_through_a_vit_equals_the_chained_abi_calls():
     import vit_vs_raw_iq_amd._native as N
     from vit_vs_raw_iq_amd import CyclicSpectrum
-    m = small_vit()
+    m = small_vit(2, 64, 64)
     cs = CyclicSpectrum.for_model(m, 1024, differentiable=True)
     plain = CyclicSpectrum.for_model(m, 1024)
     assert (cs.n_fft, cs.kind, cs.differentiable, plain.differentiable) == (64, "both", True, False)

@@ -17,11 +17,9 @@ import numpy as np
 import pytest
 import torch
 
+from frontend_gpu import dev, same_bits
+
 pytestmark = pytest.mark.gpu
-
-
-def dev():
-    return torch.device("cuda:0")
 
 
 @functools.lru_cache(maxsize=None)
@@ -57,10 +55,6 @@ def preprocess(raw, take, stats):
     N.check(N.lib().iq_frames_preprocess(raw.data_ptr(), out.data_ptr(), B, length, take, cstats(stats), N.stream_handle()),
             "iq_frames_preprocess")
     return out
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
 
 
 @pytest.mark.parametrize("length,take", [(1024, 1024), (1024, 512), (32, 32), (32, 16), (33, 33), (33, 7)])

@@ -14,17 +14,10 @@ import numpy as np
 import pytest
 import torch
 
+from frontend_gpu import dev, same_bits
 from receiver_ref import EPS, EVM_CAP, T0_CAP, abs_windows, circular_distance, complex_frames, dot_bound, evm, true_instant
 
 pytestmark = pytest.mark.gpu
-
-
-def dev():
-    return torch.device("cuda:0")
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
 
 
 def to_dev(a, dtype=torch.float32):

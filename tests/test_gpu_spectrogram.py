@@ -22,34 +22,9 @@ import pytest
 import torch
 
 import spectrogram_ref as R
-from prof_names import kernel_launches
+from frontend_gpu import GUARD, SENTINEL, abi_call, bits, dev, on_device, same_bits, small_vit
 
 pytestmark = pytest.mark.gpu
-
-GUARD = 64                     # floats in front of and behind every buffer (256 bytes: keeps the 16-byte alignment)
-SENTINEL = -12345.5
-
-
-def dev():
-    return torch.device("cuda:0")
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.int32)
-
-
-def guarded(a, fill):
-    """A copy of `a` on the device between two guards of `fill` -> (whole buffer, the part that holds a)."""
-    a = np.ascontiguousarray(a, dtype=np.float32)
-    buf = torch.full((a.size + 2 * GUARD,), fill, dtype=torch.float32, device=dev())
-    buf[GUARD:GUARD + a.size] = torch.from_numpy(a.reshape(-1)).to(dev())
-    return buf, buf[GUARD:GUARD + a.size]
-
-
-def guards_intact(buf, fill):
-    g = torch.cat([buf[:GUARD], buf[-GUARD:]]).cpu().numpy()
-    return bool(np.all(np.isnan(g))) if np.isnan(fill) else bool(np.all(g == np.float32(fill)))
-
 
 def struct(n_fft, width, hop, pad, mode=0, inv_norm=1.0, floor=1.0, scale=1.0, shift=0.0):
     import vit_vs_raw_iq_amd._native as N
@@ -63,45 +38,16 @@ def abi_forward(x, table, par, expect_kernel=True):
     call end to end, so the guards stand in front of the first and behind the last; with one frame per call (half of EXACT, and
     the single-frame calls of the independence test) they stand around that frame's samples, and a read that strays into a
     NEIGHBOURING frame shows in the exact cases (the frames differ) and in the independence test."""
-    import vit_vs_raw_iq_amd._native as N
-    L = N.lib()
     n, _, length = x.shape
-    xb, xv = guarded(x, np.nan)
-    tb, tv = guarded(table, np.nan)
-    ob, ov = guarded(np.full((n, 1, par.n_fft, par.width), SENTINEL), SENTINEL)
-
-    def run():
-        N.check(L.iq_frames_spectrogram(xv.data_ptr(), tv.data_ptr(), ov.data_ptr(), n, length, ctypes.byref(par),
-                                        N.stream_handle()), "iq_frames_spectrogram")
-    if expect_kernel:
-        assert kernel_launches(L, run) == {"spectrogram_fwd_kernel": 1}
-    else:
-        run()
-    torch.cuda.synchronize()
-    assert guards_intact(ob, SENTINEL) and guards_intact(xb, np.nan) and guards_intact(tb, np.nan)
-    return ov.cpu().numpy().reshape(n, 1, par.n_fft, par.width)
+    return abi_call("iq_frames_spectrogram", "spectrogram_fwd_kernel", (x, table), (n, 1, par.n_fft, par.width), n, length, par,
+                    expect_kernel)
 
 
 def abi_backward(x, table, dout, par, expect_kernel=True):
     """-> dx (n, 2, len) numpy through the C ABI; dx lies between sentinels and is pre-filled with the sentinel."""
-    import vit_vs_raw_iq_amd._native as N
-    L = N.lib()
     n, _, length = x.shape
-    xb, xv = guarded(x, np.nan)
-    tb, tv = guarded(table, np.nan)
-    db, dv = guarded(dout, np.nan)
-    gb, gv = guarded(np.full((n, 2, length), SENTINEL), SENTINEL)
-
-    def run():
-        N.check(L.iq_frames_spectrogram_bwd(xv.data_ptr(), tv.data_ptr(), dv.data_ptr(), gv.data_ptr(), n, length,
-                                            ctypes.byref(par), N.stream_handle()), "iq_frames_spectrogram_bwd")
-    if expect_kernel:
-        assert kernel_launches(L, run) == {"spectrogram_bwd_kernel": 1}
-    else:
-        run()
-    torch.cuda.synchronize()
-    assert guards_intact(gb, SENTINEL) and guards_intact(db, np.nan)
-    return gv.cpu().numpy().reshape(n, 2, length)
+    return abi_call("iq_frames_spectrogram_bwd", "spectrogram_bwd_kernel", (x, table, dout), (n, 2, length), n, length, par,
+                    expect_kernel)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -184,10 +130,6 @@ def test_an_offset_frame_pointer_takes_the_scalar_staging_path():
 # ---------------------------------------------------------------------------------------------------------------------------
 # 2. structure
 # ---------------------------------------------------------------------------------------------------------------------------
-def on_device(x):
-    return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(dev())
-
-
 @pytest.mark.parametrize("n_fft", [32, 96])
 def test_a_tone_peaks_in_its_fftshift_row(n_fft):
     from vit_vs_raw_iq_amd import Spectrogram
@@ -297,17 +239,10 @@ def test_log_spectrogram_and_its_gradient_against_the_fp64_definition(name):
 # ---------------------------------------------------------------------------------------------------------------------------
 # 4. through Python, 5. independence
 # ---------------------------------------------------------------------------------------------------------------------------
-def small_vit(h=32, w=64):
-    import vit_vs_raw_iq_amd as P
-    torch.manual_seed(3)
-    return P.AMCTransformerViT(in_channels=1, img_size_h=h, img_size_w=w, patch_size=16, num_classes=4, d_model=128, n_head=8,
-                               n_layers=2, ffn_hidden=512, drop_prob=0.0, device="cuda").to(dev()).eval()
-
-
 def test_x_grad_through_a_vit_equals_the_chained_abi_calls():
     import vit_vs_raw_iq_amd._native as N
     from vit_vs_raw_iq_amd import Spectrogram
-    m = small_vit()
+    m = small_vit(1, 32, 64)
     spec = Spectrogram.for_model(m, 1024)
     x0 = zscored_frames((0, 1, 2, 4, 7))
     x = x0.clone().requires_grad_(True)
@@ -351,10 +286,6 @@ def test_a_frame_does_not_depend_on_the_call_it_is_part_of():
 # 6. integration
 # ---------------------------------------------------------------------------------------------------------------------------
 STATS = {"i_mean": 0.01, "i_std": 0.9, "q_mean": -0.02, "q_std": 1.1}
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
 
 
 def direct(raw, layout, h, w, imp=None, seed=0, step=0, frame_base=0):
@@ -410,7 +341,7 @@ def test_a_vit_trains_on_spectrograms_of_fresh_frames_and_the_curve_runs():
     from vit_vs_raw_iq_amd.trainer import FusedTrainer
     fs = FrameSynth(["BPSK", "QPSK", "16QAM", "GMSK"], snrs_db=(20.0,), length=1024, seed=5, device=dev())
     stats = fs.stats(64)
-    m = small_vit().train()
+    m = small_vit(1, 32, 64).train()
     spec = Spectrogram.for_model(m, 1024)
     raw, y, _ = fs.generate(64, 0, 1)
     from vit_vs_raw_iq_amd import Impairments, impair

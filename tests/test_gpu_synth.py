@@ -22,20 +22,13 @@ import pytest
 import torch
 
 from dropout_ref import philox4x32
+from frontend_gpu import dev, same_bits
 
 pytestmark = pytest.mark.gpu
 
 SITE_SYNTH = 0xFFFFFFFE
 M32 = 0xFFFFFFFF
 FOUR = ["OOK", "BPSK", "QPSK", "16QAM"]
-
-
-def dev():
-    return torch.device("cuda:0")
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

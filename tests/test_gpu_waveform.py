@@ -22,6 +22,7 @@ import numpy as np
 import pytest
 import torch
 
+from frontend_gpu import dev, same_bits
 from waveform_ref import band_edge, host_frame, out_of_band_fraction
 
 pytestmark = pytest.mark.gpu
@@ -31,14 +32,6 @@ SHAPES = {"a": dict(length=1024, sps=8, span=8, n_phase=32, taps=3),
           "c": dict(length=8192, sps=1, span=32, n_phase=4, taps=8)}
 FRAMES = {"a": 76, "b": 76, "c": 19}
 EVERYTHING = dict(return_drawn=True, return_symbols=True, return_taps=True)
-
-
-def dev():
-    return torch.device("cuda:0")
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
 
 
 def check_integers(ws, n, frame_base, stream, frames):

@@ -14,6 +14,8 @@ Import name: `vit_vs_raw_iq_amd` (the directory name contains hyphens; the repo-
   impairments -- channel impairments on the device (phase, frequency offset, shift, gain, AWGN): augmentation and accuracy curves
   synth     -- labelled synthetic frames made on the device as a keyed stream (FrameSynth, SynthStream, train_on_stream)
   waveform  -- pulse-shaped frames on the device: RRC shaping, true OQPSK, GMSK as CPM, timing phase, multipath (ShapedSynth)
+  frontend  -- what the three image front ends below share (FrontEnd: checks, one autograd function, launch, fit, table cache)
+               and front_end, the `spectrogram=` argument of the input paths
   spectrogram -- spectrogram front end on the device: (B, 2, len) frames -> the (B, 1, n_fft, width) image of the ViT, differentiable
   cyclic    -- cyclic-spectrum front end on the device: (B, 2, len) frames -> the (B, C, n_fft, n_fft) spectral correlation image,
                differentiable on request

@@ -35,11 +35,10 @@ import ctypes as C
 import math
 
 import numpy as np
-import torch
 
 from . import _native as N
-from .impairments import _index, _number
-from .spectrogram import MAX_LENGTH, _fit, _host, _on_device
+from ._args import _index, _number
+from .frontend import FrontEnd, _host, _image_geometry, _mode
 
 PROFILES = ("gaussian", "triangle")
 MODES = ("power", "log")
@@ -63,7 +62,7 @@ def profile_table(profile, radius, n_frac, sigma=1.0):
     return t
 
 
-class Constellation:
+class Constellation(FrontEnd):
     """The geometry, profile and scaling of one front end.  Defaults: 'gaussian' with sigma in pixels and radius =
     ceil(4 sigma), capped at 16; 'triangle' has radius 1; a caller's `table` (radius * n_frac + 1 numbers, radius given or taken
     from its length) replaces both.  inv_norm = 1 / (length * s^2) with s the sum of the profile at the integer pixel distances
@@ -72,17 +71,17 @@ class Constellation:
     point stands a decade above the empty background.  Arguments are checked here, before any device work; the table goes to a
     device at the first call for that device and stays there."""
 
+    reference = "constellation_reference"
+
     def __init__(self, height, width, length, extent=3.0, profile="gaussian", sigma=1.0, radius=None, n_frac=8, table=None,
                  mode="log", floor=None, scale=1.0, shift=0.0, inv_norm=None):
         self.height, self.width = _size(height, "height"), _size(width, "width")
-        self.length = _index(length, "length", 1, MAX_LENGTH)
+        super().__init__(length)
         self.extent = _number(extent, "extent")
         if self.extent <= 0:
             raise ValueError(f"extent must be positive, got {extent!r}")
         self.n_frac = _index(n_frac, "n_frac", 1, MAX_FRAC)
-        if mode not in MODES:
-            raise ValueError(f"mode must be one of {MODES}, got {mode!r}")
-        self.mode = mode
+        self.mode = _mode(mode, MODES)
         if table is not None:
             t = np.asarray(table, dtype=np.float64).reshape(-1)
             if radius is None:
@@ -119,24 +118,18 @@ class Constellation:
                 raise ValueError(f"the profile sums to {s} over the integer pixel distances: pass inv_norm")
             inv_norm = 1.0 / (self.length * s * s)
         self.inv_norm = _number(inv_norm, "inv_norm")
-        self.floor = _number(self.inv_norm / 10.0 if floor is None else floor, "floor")
-        if self.floor <= 0 or float(np.float32(self.floor)) <= 0:
-            raise ValueError(f"floor must be positive (in fp32), got {floor!r}")
-        self.scale, self.shift = _number(scale, "scale"), _number(shift, "shift")
-        self._tables = {}
+        self._set_scaling(self.inv_norm / 10.0 if floor is None else floor, scale, shift)
 
     @property
     def n_fft(self):
-        """The image height, under the name the input paths read."""
+        """The image height, under the name the other two front ends have for it; nothing in the package reads it."""
         return self.height
 
     @classmethod
     def for_model(cls, model, length, **kw):
         """A front end whose image is the input of `model` (an AMCTransformerViT or its encoder): height = img_size_h, width =
         img_size_w, both multiples of 32."""
-        geom = getattr(getattr(model, "encoder", model), "_geom", None)
-        if not isinstance(geom, dict) or geom.get("kind") != 0:
-            raise TypeError(f"expected a ViT model (image input), got {type(model).__name__}")
+        geom = _image_geometry(model)
         if geom["in_channels"] != 1:
             raise ValueError(f"a constellation image has one channel, the model expects {geom['in_channels']}")
         return cls(geom["img_h"], geom["img_w"], length, **kw)
@@ -147,70 +140,20 @@ class Constellation:
                                mode=MODES.index(self.mode), x_scale=self.x_scale, x_off=self.x_off, y_scale=self.y_scale,
                                y_off=self.y_off, inv_norm=self.inv_norm, floor=self.floor, scale=self.scale, shift=self.shift)
 
-    def table_on(self, device):
-        """The fp32 table on `device` (uploaded once per device)."""
-        return _on_device(self._tables, self.table, device)
+    def _forward(self, x, out, B, par, stream):
+        N.check(N.lib().iq_frames_constellation(x.data_ptr(), self.table_on(x.device).data_ptr(), out.data_ptr(), B,
+                                                self.length, C.byref(par), stream), "iq_frames_constellation")
 
-    def _check(self, x, what="x"):
-        if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.shape[1] != 2 or x.shape[2] != self.length:
-            raise ValueError(f"{what} must be a (B, 2, {self.length}) tensor, got "
-                             f"{tuple(x.shape) if hasattr(x, 'shape') else x!r}")
-        if not x.is_cuda:
-            raise N.IqError("Constellation runs on the MI355X only: x is a CPU tensor and there is no CPU fallback "
-                            "(constellation_reference is the host definition used by the tests)")
-
-    def __call__(self, x):
-        """x: device (B, 2, len) fp32 -> (B, 1, height, width) fp32 on the current stream, no host synchronisation;
-        differentiable with respect to x."""
-        self._check(x)
-        return _ConstellationFn.apply(x, self)
-
-    def fit(self, x_subset):
-        """Set scale and shift so that the images of `x_subset` (device (B, 2, len)) have zero mean and unit standard deviation
-        (unbiased, floored at 1e-8): one call with scale 1 and shift 0, then a device mean / std.  One host synchronisation.
-        -> self."""
-        return _fit(self, x_subset)
+    def _backward(self, x, dout, dx, B, par, stream):
+        N.check(N.lib().iq_frames_constellation_bwd(x.data_ptr(), self.table_on(x.device).data_ptr(), dout.data_ptr(),
+                                                    dx.data_ptr(), B, self.length, C.byref(par), stream),
+                "iq_frames_constellation_bwd")
 
     def __repr__(self):
         shape = f"sigma={self.sigma}, " if self.profile == "gaussian" else ""
         return (f"Constellation(height={self.height}, width={self.width}, length={self.length}, extent={self.extent}, "
                 f"profile={self.profile!r}, {shape}radius={self.radius}, n_frac={self.n_frac}, mode={self.mode!r}, "
                 f"floor={self.floor}, scale={self.scale}, shift={self.shift})")
-
-
-def _launch_fwd(x, con):
-    x = x.contiguous().float()
-    B = x.shape[0]
-    out = torch.empty(B, 1, con.height, con.width, dtype=torch.float32, device=x.device)
-    par = con.struct()
-    if B > 0:
-        N.check(N.lib().iq_frames_constellation(x.data_ptr(), con.table_on(x.device).data_ptr(), out.data_ptr(), B, con.length,
-                                                C.byref(par), torch.cuda.current_stream(x.device).cuda_stream),
-                "iq_frames_constellation")
-    return x, out, par
-
-
-class _ConstellationFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, con):
-        x, out, par = _launch_fwd(x, con)
-        ctx.save_for_backward(x)
-        ctx.par = par                            # the scaling of THIS call: fit() may change the object before backward
-        ctx.con = con
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        (x,) = ctx.saved_tensors
-        con = ctx.con
-        dout = dout.contiguous().float()
-        dx = torch.empty_like(x)
-        if x.shape[0] > 0:
-            N.check(N.lib().iq_frames_constellation_bwd(x.data_ptr(), con.table_on(x.device).data_ptr(), dout.data_ptr(),
-                                                        dx.data_ptr(), x.shape[0], con.length, C.byref(ctx.par),
-                                                        torch.cuda.current_stream(x.device).cuda_stream),
-                    "iq_frames_constellation_bwd")
-        return dx, None
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

@@ -49,8 +49,9 @@ import numpy as np
 import torch
 
 from . import _native as N
-from .impairments import _index, _number
-from .spectrogram import FFT_STEP, MAX_FFT, MAX_LENGTH, MIN_FFT, WINDOWS, _fit, _host, _on_device, _twiddles, _window
+from ._args import _index
+from .frontend import FrontEnd, _FrontEndFn, _host, _image_geometry, _mode
+from .spectrogram import FFT_STEP, MAX_FFT, MIN_FFT, WINDOWS, _twiddles, _window
 
 KINDS = ("scf", "conj", "both")
 MODES = ("power", "log", "coherence")
@@ -63,20 +64,21 @@ def adjoint_lds_bytes(n_fft, length):
     return 4 * (2 * ((2 * length + 3) & ~3) + 67 * n_fft + 6688)
 
 
-class CyclicSpectrum:
+class CyclicSpectrum(FrontEnd):
     """The geometry and scaling of one front end.  Defaults: hop = n_fft // 4, columns = every window that lies wholly inside
     the frame with that hop and pad (at least one), inv_norm = 1 / (columns * sum w^2).  Arguments are checked here, before any
     device work; the tables go to a device at the first call for that device and stay there.  differentiable=False (the
     default) refuses an input that requires grad; True sends such an input through iq_frames_cyclic_bwd on the way back (the
     images are the same bit for bit either way)."""
 
+    reference = "cyclic_reference"
+
     def __init__(self, n_fft, length=1024, hop=None, pad=0, columns=None, window="hann", kind="both", mode="coherence",
                  floor=1e-6, scale=1.0, shift=0.0, differentiable=False):
-        self.n_fft = _index(n_fft, "n_fft", MIN_FFT, MAX_FFT)
+        self.n_fft = self.height = self.width = _index(n_fft, "n_fft", MIN_FFT, MAX_FFT)
         if self.n_fft % FFT_STEP:
             raise ValueError(f"n_fft must be a multiple of {FFT_STEP}, got {n_fft!r}")
-        self.width = self.n_fft
-        self.length = _index(length, "length", 1, MAX_LENGTH)
+        super().__init__(length)
         self.hop = self.n_fft // 4 if hop is None else _index(hop, "hop", 1, 2 ** 31 - 1)
         self.pad = _index(pad, "pad", 0, 2 ** 31 - 1)
         if columns is None:
@@ -86,14 +88,9 @@ class CyclicSpectrum:
             raise ValueError(f"window must be one of {WINDOWS}, got {window!r}")
         if kind not in KINDS:
             raise ValueError(f"kind must be one of {KINDS}, got {kind!r}")
-        if mode not in MODES:
-            raise ValueError(f"mode must be one of {MODES}, got {mode!r}")
-        self.window, self.kind, self.mode = window, kind, mode
+        self.window, self.kind, self.mode = window, kind, _mode(mode, MODES)
         self.channels = 2 if kind == "both" else 1
-        self.floor = _number(floor, "floor")
-        if self.floor <= 0 or float(np.float32(self.floor)) <= 0:
-            raise ValueError(f"floor must be positive (in fp32), got {floor!r}")
-        self.scale, self.shift = _number(scale, "scale"), _number(shift, "shift")
+        self._set_scaling(floor, scale, shift)
         if not isinstance(differentiable, bool):
             raise TypeError(f"differentiable must be a bool, got {differentiable!r}")
         if differentiable and adjoint_lds_bytes(self.n_fft, self.length) > LDS_BYTES:
@@ -107,15 +104,12 @@ class CyclicSpectrum:
         self.table = np.stack([c, s]).astype(np.float32)           # (2, n_fft, n_fft): the spectrogram's table
         ang = 2.0 * np.pi * np.arange(self.n_fft) / self.n_fft
         self.rot = np.stack([np.cos(ang), np.sin(ang)]).astype(np.float32)     # (2, n_fft)
-        self._tables, self._rots = {}, {}
 
     @classmethod
     def for_model(cls, model, length=1024, **kw):
         """A front end whose image is the input of `model` (an AMCTransformerViT or its encoder): a square image of n_fft =
         img_size_h = img_size_w; in_channels 1 gives kind 'scf' unless `kind` says 'conj', in_channels 2 gives 'both'."""
-        geom = getattr(getattr(model, "encoder", model), "_geom", None)
-        if not isinstance(geom, dict) or geom.get("kind") != 0:
-            raise TypeError(f"expected a ViT model (image input), got {type(model).__name__}")
+        geom = _image_geometry(model)
         if geom["img_h"] != geom["img_w"]:
             raise ValueError(f"a cyclic spectrum is a square image, the model expects {geom['img_h']}x{geom['img_w']}")
         if geom["in_channels"] not in (1, 2):
@@ -132,77 +126,32 @@ class CyclicSpectrum:
                         mode=MODES.index(self.mode), inv_norm=self.inv_norm, floor=self.floor, scale=self.scale,
                         shift=self.shift)
 
-    def table_on(self, device):
-        """The fp32 (c, s) table on `device` (uploaded once per device)."""
-        return _on_device(self._tables, self.table, device)
-
     def rot_on(self, device):
         """The fp32 rot table on `device` (uploaded once per device)."""
-        return _on_device(self._rots, self.rot, device)
-
-    def _check(self, x, what="x"):
-        if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.shape[1] != 2 or x.shape[2] != self.length:
-            raise ValueError(f"{what} must be a (B, 2, {self.length}) tensor, got "
-                             f"{tuple(x.shape) if hasattr(x, 'shape') else x!r}")
-        if not x.is_cuda:
-            raise N.IqError("CyclicSpectrum runs on the MI355X only: x is a CPU tensor and there is no CPU fallback "
-                            "(cyclic_reference is the host definition used by the tests)")
-        if x.requires_grad and torch.is_grad_enabled() and not self.differentiable:
-            raise RuntimeError("this CyclicSpectrum is not differentiable: build it with differentiable=True for gradients "
-                               "down to the signal, or pass x.detach()")
+        return self.table_on(device, "rot")
 
     def __call__(self, x):
         """x: device (B, 2, len) fp32 -> (B, channels, n_fft, n_fft) fp32 on the current stream, no host synchronisation;
-        with differentiable=True differentiable with respect to x."""
+        with differentiable=True differentiable with respect to x.  Nothing is recorded for backward unless a gradient is
+        wanted."""
         self._check(x)
         if x.requires_grad and torch.is_grad_enabled():
-            return _CyclicFn.apply(x, self)
-        return _launch_fwd(x.detach(), self)[1]
+            return _FrontEndFn.apply(x, self)
+        return self._launch(x.detach())[1]
 
-    def fit(self, x_subset):
-        """Set scale and shift so that the images of `x_subset` (device (B, 2, len)) have zero mean and unit standard deviation
-        (unbiased, floored at 1e-8): one call with scale 1 and shift 0, then a device mean / std.  One host synchronisation.
-        -> self."""
-        return _fit(self, x_subset)
+    def _forward(self, x, out, B, par, stream):
+        N.check(N.lib().iq_frames_cyclic(x.data_ptr(), self.table_on(x.device).data_ptr(), self.rot_on(x.device).data_ptr(),
+                                         out.data_ptr(), B, self.length, C.byref(par), stream), "iq_frames_cyclic")
+
+    def _backward(self, x, dout, dx, B, par, stream):
+        N.check(N.lib().iq_frames_cyclic_bwd(x.data_ptr(), self.table_on(x.device).data_ptr(), self.rot_on(x.device).data_ptr(),
+                                             dout.data_ptr(), dx.data_ptr(), B, self.length, C.byref(par), stream),
+                "iq_frames_cyclic_bwd")
 
     def __repr__(self):
         return (f"CyclicSpectrum(n_fft={self.n_fft}, length={self.length}, hop={self.hop}, pad={self.pad}, "
                 f"columns={self.columns}, window={self.window!r}, kind={self.kind!r}, mode={self.mode!r}, floor={self.floor}, "
                 f"scale={self.scale}, shift={self.shift}, differentiable={self.differentiable})")
-
-
-def _launch_fwd(x, cs):
-    x = x.contiguous().float()
-    B = x.shape[0]
-    out = torch.empty(B, cs.channels, cs.n_fft, cs.n_fft, dtype=torch.float32, device=x.device)
-    par = cs.struct()
-    if B > 0:
-        N.check(N.lib().iq_frames_cyclic(x.data_ptr(), cs.table_on(x.device).data_ptr(), cs.rot_on(x.device).data_ptr(),
-                                         out.data_ptr(), B, cs.length, C.byref(par),
-                                         torch.cuda.current_stream(x.device).cuda_stream), "iq_frames_cyclic")
-    return x, out
-
-
-class _CyclicFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, cs):
-        x, out = _launch_fwd(x, cs)
-        ctx.save_for_backward(x)
-        ctx.par = cs.struct()                    # the scaling of THIS call: fit() may change the object before backward
-        ctx.cs = cs
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        (x,) = ctx.saved_tensors
-        cs = ctx.cs
-        dout = dout.contiguous().float()
-        dx = torch.empty_like(x)
-        if x.shape[0] > 0:
-            N.check(N.lib().iq_frames_cyclic_bwd(x.data_ptr(), cs.table_on(x.device).data_ptr(), cs.rot_on(x.device).data_ptr(),
-                                                 dout.data_ptr(), dx.data_ptr(), x.shape[0], cs.length, C.byref(ctx.par),
-                                                 torch.cuda.current_stream(x.device).cuda_stream), "iq_frames_cyclic_bwd")
-        return dx, None
 
 
 def _channelized(x, cs, table=None, rot=None):

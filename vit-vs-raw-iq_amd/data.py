@@ -192,9 +192,9 @@ class DeviceInputPipeline:
     step computes, and `iq_frames_preprocess` produces the `(B,1,H,W)` ViT image or the `(B,2,len)` raw-IQ tensor on
     the compute stream.  With `augment` (an impairments.Impairments, e.g. Impairments.augmentation()) the same launch slot
     runs `iq_frames_impair` instead: every `get()` draws fresh channel impairments keyed by (`seed`, step = the number of
-    earlier `get()` calls or `get(step=...)`, frame index in the batch).  With `spectrogram` (a spectrogram.Spectrogram; layout
-    'vit') that launch keeps the whole frame (take = len) and the spectrogram follows on the same stream: the result is its
-    `(B,1,n_fft,width)` image, h and w are not used.  No CPU fallback: construction fails without the HIP library / a GPU."""
+    earlier `get()` calls or `get(step=...)`, frame index in the batch).  With `spectrogram` (any frontend.FrontEnd; layout
+    'vit') that launch keeps the whole frame (take = len) and the front end follows on the same stream: the result is its
+    `(B,channels,height,width)` image, h and w are not used.  No CPU fallback: construction fails without the HIP library / a GPU."""
 
     def __init__(self, stats: dict, layout: str, batch: int, length: int = 1024, h: int = 32, w: int = 64, device="cuda",
                  augment=None, seed: int = 0, spectrogram=None):
@@ -206,9 +206,9 @@ class DeviceInputPipeline:
         self._N, self._L, self._torch = N, N.lib(), torch
         self.layout, self.length, self.h, self.w = layout, length, h, w
         if spectrogram is not None:
-            from .impairments import _front_end
-            _front_end(spectrogram, layout, length)
-            h, w = self.h, self.w = spectrogram.n_fft, spectrogram.width
+            from .frontend import front_end
+            front_end(spectrogram, layout, length)
+            h, w = self.h, self.w = spectrogram.height, spectrogram.width
         self._spectrogram = spectrogram
         self.take = length if layout == "rawiq" or spectrogram is not None else h * w // 2
         if self.take > length:

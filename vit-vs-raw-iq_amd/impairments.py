@@ -28,26 +28,17 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-import numbers
-import operator
 
 import numpy as np
 import torch
 
 from . import _native as N
+from ._args import _flag, _index, _number
+from .frontend import front_end
 from .saliency import _batch, _classes, _forward, _resolve
 
 KINDS = ("snr_db", "phase", "cfo", "shift", "gain_db")
-_F32_MAX = 3.4028234663852886e38
-
-
-def _number(v, what):
-    if isinstance(v, bool) or not isinstance(v, numbers.Real):
-        raise TypeError(f"{what} must be a number, got {v!r}")
-    v = float(v)
-    if not math.isfinite(v) or abs(v) > _F32_MAX:
-        raise ValueError(f"{what} must be finite, got {v!r}")
-    return v
+_front_end = front_end       # the name this function had while it lived here
 
 
 def _range(v, what):
@@ -63,24 +54,6 @@ def _range(v, what):
         return lo, hi
     v = _number(v, what)
     return v, v
-
-
-def _flag(v, what):
-    if not isinstance(v, bool) and not (isinstance(v, int) and v in (0, 1)):
-        raise TypeError(f"{what} must be True or False, got {v!r}")
-    return bool(v)
-
-
-def _index(v, what, lo=0, hi=None):
-    if isinstance(v, bool):
-        raise TypeError(f"{what} must be an integer, got {v!r}")
-    try:
-        i = operator.index(v)
-    except TypeError:
-        raise TypeError(f"{what} must be an integer, got {v!r}") from None
-    if i < lo or (hi is not None and i > hi):
-        raise ValueError(f"{what} must be >= {lo}" + (f" and <= {hi}" if hi is not None else "") + f", got {v!r}")
-    return i
 
 
 class Impairments:
@@ -150,37 +123,18 @@ def _take(layout, length, h, w):
     return take
 
 
-def _front_end(spectrogram, layout, length):
-    """The `spectrogram=` argument of an input path: None, or a spectrogram.Spectrogram, cyclic.CyclicSpectrum or
-    constellation.Constellation for frames of `length` samples, which needs layout 'vit' (the launch in front of it then runs
-    with take = len and the image is (B, 1, n_fft, width), for a CyclicSpectrum (B, channels, n_fft, n_fft), for a Constellation
-    (B, 1, height, width))."""
-    if spectrogram is None:
-        return None
-    from .constellation import Constellation
-    from .cyclic import CyclicSpectrum
-    from .spectrogram import Spectrogram
-    if not isinstance(spectrogram, (Spectrogram, CyclicSpectrum, Constellation)):
-        raise TypeError(f"spectrogram must be a Spectrogram or None, got {type(spectrogram).__name__}")
-    if layout != "vit":
-        raise ValueError(f"a spectrogram is an image: layout must be 'vit', got {layout!r}")
-    if spectrogram.length != length:
-        raise ValueError(f"the spectrogram was built for frames of {spectrogram.length} samples, these have {length}")
-    return spectrogram
-
-
 def impair(raw, stats, layout, imp, seed=0, step=0, frame_base=0, h=32, w=64, return_drawn=False, spectrogram=None):
     """raw: device (B, len, 2) fp32 frames -> the model input, (B, 1, h, w) for layout 'vit' or (B, 2, len) for 'rawiq'; with
     return_drawn also the fp32 (B, 8) table {theta, f, k, conj, s, g, snr_db, sigma per component} the kernel used.  With
-    `spectrogram` (a spectrogram.Spectrogram; layout 'vit') the whole impaired frame goes through it on the same stream and the
-    result is its (B, 1, n_fft, width) image: h and w are not used."""
+    `spectrogram` (any frontend.FrontEnd; layout 'vit') the whole impaired frame goes through it on the same stream and the
+    result is its (B, channels, height, width) image: h and w are not used."""
     if not isinstance(imp, Impairments):
         raise TypeError(f"imp must be an Impairments, got {type(imp).__name__}")
     if not isinstance(raw, torch.Tensor) or raw.dim() != 3 or raw.shape[2] != 2:
         raise ValueError(f"raw must be a (B, len, 2) tensor, got {tuple(raw.shape) if hasattr(raw, 'shape') else raw!r}")
     st = (C.c_float * 4)(*_stats4(stats))
     B, length = raw.shape[0], raw.shape[1]
-    spec = _front_end(spectrogram, layout, length)
+    spec = front_end(spectrogram, layout, length)
     take = _take(layout, length, h, w) if spec is None else length
     if imp.shift_max >= max(length, 1):
         raise ValueError(f"shift_max {imp.shift_max} must be below the frame length {length}")
@@ -235,8 +189,8 @@ def impairment_curve(model, raw, labels, stats, kind, values, layout=None, base=
     nothing else).  Chunks of `batch` frames go through `impair` with frame_base = the chunk's start and step 0, then through an
     eval forward of the plan model(x) uses, so the result does not depend on `batch`; one host synchronisation per value.  A
     fixed shift is a roll of the raw chunk on the device in front of the kernel, which composes with a random shift of `base`.
-    The module's `training` flag is left alone.  With `spectrogram` (a spectrogram.Spectrogram whose n_fft x width is the
-    image of the ViT) every impaired frame becomes its spectrogram in front of the model."""
+    The module's `training` flag is left alone.  With `spectrogram` (any frontend.FrontEnd whose height x width is the
+    image of the ViT) every impaired frame becomes its image in front of the model."""
     if kind not in KINDS:
         raise ValueError(f"kind must be one of {KINDS}, got {kind!r}")
     enc, plan_of, K = _resolve(model)
@@ -257,11 +211,11 @@ def impairment_curve(model, raw, labels, stats, kind, values, layout=None, base=
         raise ValueError(f"raw must be a (N, len, 2) tensor, got {tuple(raw.shape) if hasattr(raw, 'shape') else raw!r}")
     n, length = raw.shape[0], raw.shape[1]
     h, w = (geom["img_h"], geom["img_w"]) if own == "vit" else (0, 0)
-    spec = _front_end(spectrogram, layout, length)
+    spec = front_end(spectrogram, layout, length)
     if spec is None:
         _take(layout, length, h, w)
-    elif (spec.n_fft, spec.width) != (h, w):
-        raise ValueError(f"the spectrogram is {spec.n_fft}x{spec.width}, the model's image {h}x{w}")
+    elif (spec.height, spec.width) != (h, w):
+        raise ValueError(f"the spectrogram is {spec.height}x{spec.width}, the model's image {h}x{w}")
     for _, roll in settings:
         if roll >= max(length, 1):
             raise ValueError(f"shift {roll} must be below the frame length {length}")

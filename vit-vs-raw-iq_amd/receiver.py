@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from . import _native as N
-from .impairments import _flag, _index, _number
+from ._args import _flag, _index, _number
 from .synth import MAX_LENGTH, FrameSynth
 from .waveform import ShapedSynth, rrc_pulse
 

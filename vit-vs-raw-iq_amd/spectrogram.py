@@ -25,14 +25,13 @@ import ctypes as C
 import math
 
 import numpy as np
-import torch
 
 from . import _native as N
-from .impairments import _index, _number
+from ._args import _index
+from .frontend import FrontEnd, _host, _image_geometry, _mode
 
 WINDOWS = ("hann", "rect")
 MODES = ("power", "log")
-MAX_LENGTH = 8192            # one workgroup keeps one frame in LDS: len * 8 bytes <= 64 KB
 MIN_FFT, MAX_FFT, FFT_STEP = 32, 256, 32
 
 
@@ -50,68 +49,38 @@ def _twiddles(n_fft, w):
     return w[:, None] * np.cos(ang), w[:, None] * np.sin(ang)
 
 
-def _on_device(cache, host, device):
-    """The numpy table `host` as a tensor on `device`, uploaded once per device (`cache`: {device: tensor})."""
-    device = torch.device(device)
-    if device.type == "cuda" and device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    t = cache.get(device)
-    if t is None:
-        t = cache[device] = torch.from_numpy(host).to(device)
-    return t
-
-
-def _fit(front, x_subset):
-    """fit() of a front end (a Spectrogram or a CyclicSpectrum): one call with scale 1 and shift 0, then a device mean / std."""
-    front._check(x_subset, "x_subset")
-    if x_subset.shape[0] < 1:
-        raise ValueError("x_subset is empty")
-    front.scale, front.shift = 1.0, 0.0
-    with torch.no_grad():
-        std, mean = torch.std_mean(front(x_subset))
-    mean, std = float(mean), max(float(std), 1e-8)
-    front.scale, front.shift = _number(1.0 / std, "scale"), _number(-mean / std, "shift")
-    return front
-
-
-class Spectrogram:
+class Spectrogram(FrontEnd):
     """The geometry and scaling of one front end.  Defaults: hop = max(1, length // width), pad = max(0, ceil(((width-1)*hop +
     n_fft - length) / 2)) (the windows are centred on the frame), inv_norm = 1 / sum w^2.  Arguments are checked here, before
     any device work; the table goes to a device at the first call for that device and stays there."""
 
+    reference = "spectrogram_reference"
+
     def __init__(self, n_fft, width, length=1024, hop=None, pad=None, window="hann", mode="log", floor=1e-3, scale=1.0,
                  shift=0.0):
-        self.n_fft = _index(n_fft, "n_fft", MIN_FFT, MAX_FFT)
+        self.n_fft = self.height = _index(n_fft, "n_fft", MIN_FFT, MAX_FFT)
         if self.n_fft % FFT_STEP:
             raise ValueError(f"n_fft must be a multiple of {FFT_STEP}, got {n_fft!r}")
         self.width = _index(width, "width", 1, 2 ** 31 - 1)
-        self.length = _index(length, "length", 1, MAX_LENGTH)
+        super().__init__(length)
         self.hop = max(1, self.length // self.width) if hop is None else _index(hop, "hop", 1, 2 ** 31 - 1)
         if pad is None:
             pad = max(0, -((self.length - (self.width - 1) * self.hop - self.n_fft) // 2))
         self.pad = _index(pad, "pad", 0, 2 ** 31 - 1)
         if window not in WINDOWS:
             raise ValueError(f"window must be one of {WINDOWS}, got {window!r}")
-        if mode not in MODES:
-            raise ValueError(f"mode must be one of {MODES}, got {mode!r}")
-        self.window, self.mode = window, mode
-        self.floor = _number(floor, "floor")
-        if self.floor <= 0 or float(np.float32(self.floor)) <= 0:
-            raise ValueError(f"floor must be positive (in fp32), got {floor!r}")
-        self.scale, self.shift = _number(scale, "scale"), _number(shift, "shift")
+        self.window, self.mode = window, _mode(mode, MODES)
+        self._set_scaling(floor, scale, shift)
         w = _window(window, self.n_fft)
         self.inv_norm = 1.0 / float(np.sum(w * w))
         c, s = _twiddles(self.n_fft, w)
         self.table = np.stack([c, s]).astype(np.float32)           # (2, n_fft, n_fft): the kernel's table
-        self._tables = {}
 
     @classmethod
     def for_model(cls, model, length=1024, **kw):
         """A front end whose image is the input of `model` (an AMCTransformerViT or its encoder): n_fft = img_size_h, width =
         img_size_w."""
-        geom = getattr(getattr(model, "encoder", model), "_geom", None)
-        if not isinstance(geom, dict) or geom.get("kind") != 0:
-            raise TypeError(f"expected a ViT model (image input), got {type(model).__name__}")
+        geom = _image_geometry(model)
         if geom["in_channels"] != 1:
             raise ValueError(f"a spectrogram has one channel, the model expects {geom['in_channels']}")
         return cls(geom["img_h"], geom["img_w"], length, **kw)
@@ -121,72 +90,18 @@ class Spectrogram:
         return N.Spectrogram(n_fft=self.n_fft, hop=self.hop, pad=self.pad, width=self.width, mode=MODES.index(self.mode),
                              inv_norm=self.inv_norm, floor=self.floor, scale=self.scale, shift=self.shift)
 
-    def table_on(self, device):
-        """The fp32 table on `device` (uploaded once per device)."""
-        return _on_device(self._tables, self.table, device)
+    def _forward(self, x, out, B, par, stream):
+        N.check(N.lib().iq_frames_spectrogram(x.data_ptr(), self.table_on(x.device).data_ptr(), out.data_ptr(), B,
+                                              self.length, C.byref(par), stream), "iq_frames_spectrogram")
 
-    def _check(self, x, what="x"):
-        if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.shape[1] != 2 or x.shape[2] != self.length:
-            raise ValueError(f"{what} must be a (B, 2, {self.length}) tensor, got "
-                             f"{tuple(x.shape) if hasattr(x, 'shape') else x!r}")
-        if not x.is_cuda:
-            raise N.IqError("Spectrogram runs on the MI355X only: x is a CPU tensor and there is no CPU fallback "
-                            "(spectrogram_reference is the host definition used by the tests)")
-
-    def __call__(self, x):
-        """x: device (B, 2, len) fp32 -> (B, 1, n_fft, width) fp32 on the current stream, no host synchronisation;
-        differentiable with respect to x."""
-        self._check(x)
-        return _SpectrogramFn.apply(x, self)
-
-    def fit(self, x_subset):
-        """Set scale and shift so that the images of `x_subset` (device (B, 2, len)) have zero mean and unit standard deviation
-        (unbiased, floored at 1e-8): one call with scale 1 and shift 0, then a device mean / std.  One host synchronisation.
-        -> self."""
-        return _fit(self, x_subset)
+    def _backward(self, x, dout, dx, B, par, stream):
+        N.check(N.lib().iq_frames_spectrogram_bwd(x.data_ptr(), self.table_on(x.device).data_ptr(), dout.data_ptr(),
+                                                  dx.data_ptr(), B, self.length, C.byref(par), stream),
+                "iq_frames_spectrogram_bwd")
 
     def __repr__(self):
         return (f"Spectrogram(n_fft={self.n_fft}, width={self.width}, length={self.length}, hop={self.hop}, pad={self.pad}, "
                 f"window={self.window!r}, mode={self.mode!r}, floor={self.floor}, scale={self.scale}, shift={self.shift})")
-
-
-def _launch_fwd(x, spec):
-    x = x.contiguous().float()
-    B = x.shape[0]
-    out = torch.empty(B, 1, spec.n_fft, spec.width, dtype=torch.float32, device=x.device)
-    par = spec.struct()
-    if B > 0:
-        N.check(N.lib().iq_frames_spectrogram(x.data_ptr(), spec.table_on(x.device).data_ptr(), out.data_ptr(), B,
-                                              spec.length, C.byref(par), torch.cuda.current_stream(x.device).cuda_stream),
-                "iq_frames_spectrogram")
-    return x, out
-
-
-class _SpectrogramFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, spec):
-        x, out = _launch_fwd(x, spec)
-        ctx.save_for_backward(x)
-        ctx.par = spec.struct()                  # the scaling of THIS call: fit() may change the object before backward
-        ctx.spec = spec
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        (x,) = ctx.saved_tensors
-        spec = ctx.spec
-        dout = dout.contiguous().float()
-        dx = torch.empty_like(x)
-        if x.shape[0] > 0:
-            N.check(N.lib().iq_frames_spectrogram_bwd(x.data_ptr(), spec.table_on(x.device).data_ptr(), dout.data_ptr(),
-                                                      dx.data_ptr(), x.shape[0], spec.length, C.byref(ctx.par),
-                                                      torch.cuda.current_stream(x.device).cuda_stream),
-                    "iq_frames_spectrogram_bwd")
-        return dx, None
-
-
-def _host(a):
-    return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
 
 
 def _columns(spec, length):

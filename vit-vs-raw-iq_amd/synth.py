@@ -32,7 +32,9 @@ import torch
 
 from . import _native as N
 from . import data as D
-from .impairments import Impairments, _flag, _front_end, _index, _number, _stats4, _take
+from ._args import _flag, _index, _number
+from .frontend import front_end
+from .impairments import Impairments, _stats4, _take
 
 KIND_POINTS, KIND_GMSK, KIND_OQPSK = 0, 1, 2
 SHAPED = {"GMSK": KIND_GMSK, "OQPSK": KIND_OQPSK}
@@ -218,9 +220,9 @@ class SynthStream:
     """Batches of a FrameSynth stream as model input: get(step) makes frames [step * batch, (step + 1) * batch) of `stream` and
     passes them through iq_frames_preprocess (z-score with `stats`, layout 'vit' (B, 1, h, w) or 'rawiq' (B, 2, len)) or, with
     `augment` (an impairments.Impairments), through iq_frames_impair with the synth's seed, step word = `stream` and the same
-    frame_base.  With `spectrogram` (a spectrogram.Spectrogram; layout 'vit') that launch keeps the whole frame (take = len) and
-    the spectrogram follows: x is its (batch, 1, n_fft, width) image, h and w are not used.  All on the current stream of the
-    device, no host synchronisation."""
+    frame_base.  With `spectrogram` (any frontend.FrontEnd; layout 'vit') that launch keeps the whole frame (take = len) and
+    the front end follows: x is its (batch, channels, height, width) image, h and w are not used.  All on the current stream of
+    the device, no host synchronisation."""
 
     def __init__(self, synth: FrameSynth, stats, layout: str, batch: int, h: int = 32, w: int = 64, stream: int = 0,
                  augment=None, spectrogram=None):
@@ -228,11 +230,11 @@ class SynthStream:
             raise TypeError(f"synth must be a FrameSynth, got {type(synth).__name__}")
         self.synth, self.layout, self.h, self.w = synth, layout, h, w
         self._stats = (C.c_float * 4)(*_stats4(stats))
-        self.spectrogram = _front_end(spectrogram, layout, synth.length)
+        self.spectrogram = front_end(spectrogram, layout, synth.length)
         if self.spectrogram is None:
             self.take = _take(layout, synth.length, h, w)
         else:
-            self.take, self.h, self.w = synth.length, self.spectrogram.n_fft, self.spectrogram.width
+            self.take, self.h, self.w = synth.length, self.spectrogram.height, self.spectrogram.width
         self.batch = _index(batch, "batch", 1, 2 ** 31 - 1)
         self.stream = _index(stream, "stream", 0, 2 ** 32 - 1)
         if augment is not None:

@@ -27,7 +27,7 @@ import torch
 
 from . import _native as N
 from . import data as D
-from .impairments import _flag, _index, _number
+from ._args import _flag, _index, _number
 from .synth import KIND_GMSK, KIND_OQPSK, KIND_POINTS, FrameSynth
 
 MAX_SPS, MAX_SPAN, MAX_PHASE, MAX_TAPS = 16, 32, 64, 8      # the limits of iq_frames_waveform
