@@ -639,6 +639,69 @@ int iq_frames_constellation(const float* x /*[n,2,len]*/, const float* table /*D
 int iq_frames_constellation_bwd(const float* x, const float* table, const float* dout /*[n,1,height,width]*/,
                                 float* dx /*[n,2,len]*/, int n_frames, int len, const iq_constellation_t* par,
                                 iq_stream_t stream);
+/* Carrier recovery (csrc/carrier.hip): a blind frequency and phase estimate per frame from the spectral line of the M-th power
+ * (M-PSK / QAM modulation drops out of z^M and leaves a line at M f), and the derotation.  It sits between the receiver and the
+ * constellation.  x and out are fp32 frames of len samples, planar = 0: [n_frames, len, 2]; planar = 1: [n_frames, 2, len];
+ * z[n] = I[n] + j Q[n].  t1, t2 and tw are DEVICE tables, plain numbers to the kernel (carrier.py fills them with t[0][m][k] =
+ * cos(2 pi m k / n), t[1][m][k] = sin(2 pi m k / n) and tw[0][i] = cos(2 pi i / N), tw[1][i] = sin(2 pi i / N), computed in fp64
+ * from integer numerators and rounded; W below is then the N-point DFT of w).  Phases are integers in units of 2^-32 turn, as in
+ * iq_frames_waveform: e(p) = (cos, sin)(pi x), x = (float)(int32)p * 2^-31.  rot(v, c, s) = v (c + j s) = (fmaf(v.re, c,
+ * -(v.im * s)), fmaf(v.re, s, v.im * c)), the inner products rounded.  Per frame, in this order (IQ_CR_ESTIMATE):
+ *   1. w[n] = z[n]^M by log2 M squarings, each v <- rot(v, v.re, v.im); w[n] = 0 for len <= n < N, N = n1 n2.
+ *   2. With n = a n2 + b (a < n1, b < n2) and k = k1 + n1 k2 (k1 < n1, k2 < n2):
+ *        A[k1,b]  = sum_a w[a n2 + b] (c1 - j s1)[a][k1]
+ *        Bm[k1,b] = rot(A[k1,b], twc[b k1], -tws[b k1])          (b k1 < N always)
+ *        W[k]     = sum_b Bm[k1,b] (c2 - j s2)[b][k2]
+ *      Both sums are fp32-input MFMA products, i.e. per output an fp32 fmaf chain from +0 over the summation index ascending,
+ *      for each pair (m, m+1) of it the two c products before the two s products: Re: c Re(v), s Im(v); Im: c Im(v), -s Re(v).
+ *   3. P[k] = fmaf(Im W, Im W, Re W * Re W); written to power[frame][k], k = 0 .. N-1 in natural order, when power is not NULL.
+ *   4. Peak: s^ = the first maximum of P[s mod N] over the signed bins s = -k_max .. min(k_max, N/2 - 1) ascending (a NaN counts
+ *      as +infinity), k^ = s^ mod N, b = P[k^].  If b is 0 or not finite: F = TH = 0, d = 0, est[1] = est[3] = 0, steps 5 to 7
+ *      are skipped and out = rot(z, 1, -0).
+ *   5. Refinement (refine = 1): a = P[(k^ - 1) mod N], c = P[(k^ + 1) mod N] (neighbours outside the search range count), den =
+ *      (a - (b + b)) + c, d = min(max((0.5 (a - c)) / den, -0.5), 0.5) when den < 0 and finite, else 0; every operation
+ *      rounded to fp32.  refine = 0: d = 0.
+ *   6. F = (int32) rint((s^ + d) / (N M) * 2^32) in double, wrapping: the carrier frequency in units of 2^-32 cycle per sample.
+ *   7. G = F M (wrapping); S = sum_{n < len} rot(w[n], cos, -sin of e(G n)), real and imaginary parts added separately: thread
+ *      n % 256 its samples n ascending, then the wave's butterfly, then the four wave sums in order; sum |w|^2 likewise with
+ *      fmaf(Im, Im, fmaf(Re, Re, acc)).  TH = (int32) rint(atan2(Im S, Re S) / (2 pi M) * 2^32) in double, wrapping.
+ *   8. out[n] = rot(z[n], c, -s), (c, s) = e(F n + TH) (wrapping).  The M-th-power line of out is then real and positive at bin
+ *      0, up to the resolution of the estimate.
+ * What remains: the M-fold ambiguity (the estimate fixes M times the phase: out is the constellation turned by an unknown multiple
+ * of 2 pi / M, and F is known modulo 1 / M cycle per sample), and the constellation's own M-th-power angle (sum a^M of a
+ * diagonal QPSK is negative: its points come out on the axes, turned by pi / 4).
+ * Outputs: est: NULL or fp32 [n_frames, 4] = {F 2^-32 (cycles per sample), TH 2^-32 2 pi (radians), s^ + d (bins of the M-th
+ * power), |S|^2 / (len sum |w|^2): a lock quality in [0, 1], 0 when the denominator is 0}; fth_out: NULL or int32 [n_frames, 2]
+ * = {F, TH}.  IQ_CR_GIVEN: F and TH are par->fth[frame], only step 8 runs, no table is read (t1, t2, tw may be NULL); fth_out
+ * repeats them, est = {F 2^-32, TH 2^-32 2 pi, NaN, NaN}.  No atomics: two runs agree bit for bit, and a frame's outputs depend on
+ * neither n_frames nor its position.  Nothing is allocated, the host is not synchronised.
+ * iq_frames_carrier_bwd: dx[n] = rot(dout[n], c, s), (c, s) = e(F n + TH), F and TH from par->fth whatever par->mode says: the
+ * adjoint with the estimate held fixed (pass the forward's fth_out), as the receiver holds its timing.  dout, dx in x's layout.
+ * One workgroup per frame.  LDS: w and Bm, planar, 16 N bytes, and one padding word per row of Bm (8 n2 bytes: the second stage
+ * reads Bm transposed relative to how the first writes it), at most 128.3 KB of 160 KB; P takes w's place once stage 1 has
+ * consumed it, and z is read from memory again for steps 7 and 8.
+ * IQ_STATUS_ARG before any launch, outputs untouched: NULL x / out / dout / dx / par; order outside {1,2,4,8}; refine, planar
+ * outside {0,1}; mode outside IQ_CR_*; len < 1; k_max outside [0, N/2]; x / out / dout / dx not 8-byte (planar = 0) or 4-byte
+ * (planar = 1) aligned, any other pointer not 4-byte aligned; NULL t1 / t2 / tw with IQ_CR_ESTIMATE; NULL fth with IQ_CR_GIVEN or
+ * in the backward; a non-NULL power with IQ_CR_GIVEN.  IQ_STATUS_UNSUPPORTED: n1 or n2 not a multiple of 32 in [32, 256], N < len,
+ * N > 8192, len * 8 bytes above 64 KB.  n_frames <= 0: success, nothing is launched. */
+enum { IQ_CR_GIVEN = 0, IQ_CR_ESTIMATE = 1 };
+typedef struct iq_carrier {
+  int order;      /* M in {1,2,4,8} */
+  int n1, n2;     /* DFT size N = n1*n2, each a multiple of 32 in [32,256]; N >= len */
+  int k_max;      /* search signed bins s in [-k_max, min(k_max, N/2-1)], 0 <= k_max <= N/2 */
+  int refine;     /* 1: parabolic interpolation of the peak */
+  int planar;     /* 0: x,out [n,len,2]; 1: [n,2,len] */
+  int mode;       /* IQ_CR_* */
+  const float* t1;     /* DEVICE fp32 [2][n1][n1] = (c,s)[m][k] */
+  const float* t2;     /* DEVICE fp32 [2][n2][n2] */
+  const float* tw;     /* DEVICE fp32 [2][N] */
+  const int32_t* fth;  /* DEVICE int32 [n,2] = {F, TH}: IQ_CR_GIVEN and the backward */
+} iq_carrier_t;
+int iq_frames_carrier(const float* x, float* out, float* est /*NULL or [n,4]*/, int32_t* fth_out /*NULL or [n,2]*/,
+                      float* power /*NULL or [n,N]; must be NULL when GIVEN*/, int n_frames, int len,
+                      const iq_carrier_t* par, iq_stream_t stream);
+int iq_frames_carrier_bwd(const float* dout, float* dx, int n_frames, int len, const iq_carrier_t* par, iq_stream_t stream);
 int iq_patchify(const float* src, void* patches, int kind, int B, int C, int H, int W, int p, int Kpad,
                 iq_stream_t stream);
 int iq_cls_rows(const float* cls, const float* pe, void* x0, int B, int S, int D, const iq_dropout_t* drop,

@@ -21,6 +21,8 @@ Import name: `vit_vs_raw_iq_amd` (the directory name contains hyphens; the repo-
                differentiable on request
   constellation -- constellation front end on the device: (B, 2, len) points -> the (B, 1, height, width) density image, differentiable
   receiver  -- receiver on the device: matched filter, timing estimate, one sample per symbol, differentiable (Receiver, ReceivedSynth)
+  carrier   -- carrier recovery on the device: blind frequency and phase estimate from the M-th-power line, derotation,
+               differentiable (Carrier), and Synchronised, a front end behind it
   _native   -- ctypes binding of include/iqvit.h  (libiqvit.so; no fallback)
   ViT.models.amc_transformer / transformer_rawIQ.models.transformer_rawIQ
             -- import paths used by the reference's scripts (hyperparameter_tuning.py:19,37)
@@ -41,6 +43,7 @@ from .cyclic import CyclicSpectrum, cyclic_reference, cyclic_reference_bwd
 from .constellation import Constellation, constellation_reference, constellation_reference_bwd
 from .receiver import (Receiver, ReceivedSynth, mf_table, receiver_reference, receiver_reference_bwd,
                        transmitted_index)
+from .carrier import Carrier, Synchronised, carrier_reference, carrier_reference_bwd, dft_tables
 
 __all__ = ["AMCTransformerViT", "AMCTransformerRawIQ", "EncoderViT", "EncoderRawIQ", "EncoderLayer", "LayerNorm",
            "MultiHeadAttention", "PositionwiseFeedForward", "ScaleDotProductAttention", "PatchEmbedding",
@@ -50,4 +53,5 @@ __all__ = ["AMCTransformerViT", "AMCTransformerRawIQ", "EncoderViT", "EncoderRaw
            "SynthStream", "synth_reference", "train_on_stream", "Spectrogram", "spectrogram_reference", "spectrogram_reference_bwd",
            "ShapedSynth", "rrc_table", "gmsk_table", "waveform_reference", "Receiver", "ReceivedSynth", "mf_table", "receiver_reference",
            "receiver_reference_bwd", "transmitted_index", "CyclicSpectrum", "cyclic_reference", "cyclic_reference_bwd",
-           "Constellation", "constellation_reference", "constellation_reference_bwd"]
+           "Constellation", "constellation_reference", "constellation_reference_bwd", "Carrier", "Synchronised", "carrier_reference",
+           "carrier_reference_bwd", "dft_tables"]

@@ -66,6 +66,12 @@ class Constellation(C.Structure):
                 ("inv_norm", C.c_float), ("floor", C.c_float), ("scale", C.c_float), ("shift", C.c_float)]
 
 
+class Carrier(C.Structure):
+    _fields_ = [("order", C.c_int), ("n1", C.c_int), ("n2", C.c_int), ("k_max", C.c_int), ("refine", C.c_int),
+                ("planar", C.c_int), ("mode", C.c_int), ("t1", C.c_void_p), ("t2", C.c_void_p), ("tw", C.c_void_p),
+                ("fth", C.c_void_p)]
+
+
 class Cyclic(C.Structure):
     _fields_ = [("n_fft", C.c_int), ("hop", C.c_int), ("pad", C.c_int), ("columns", C.c_int), ("kind", C.c_int),
                 ("mode", C.c_int), ("inv_norm", C.c_float), ("floor", C.c_float), ("scale", C.c_float), ("shift", C.c_float)]
@@ -159,6 +165,8 @@ SIGNATURES = {
     "iq_frames_cyclic_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, C.POINTER(Cyclic), _P]),
     "iq_frames_constellation": (_I, [_P, _P, _P, _I, _I, C.POINTER(Constellation), _P]),
     "iq_frames_constellation_bwd": (_I, [_P, _P, _P, _P, _I, _I, C.POINTER(Constellation), _P]),
+    "iq_frames_carrier": (_I, [_P, _P, _P, _P, _P, _I, _I, C.POINTER(Carrier), _P]),
+    "iq_frames_carrier_bwd": (_I, [_P, _P, _I, _I, C.POINTER(Carrier), _P]),
     "iq_patchify": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "iq_cls_rows": (_I, [_P, _P, _P, _I, _I, _I, C.POINTER(Dropout), _P]),
     "iq_embed_bwd_gather": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, C.POINTER(Dropout), _I, _P]),
