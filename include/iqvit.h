@@ -702,6 +702,53 @@ int iq_frames_carrier(const float* x, float* out, float* est /*NULL or [n,4]*/, 
                       float* power /*NULL or [n,N]; must be NULL when GIVEN*/, int n_frames, int len,
                       const iq_carrier_t* par, iq_stream_t stream);
 int iq_frames_carrier_bwd(const float* dout, float* dx, int n_frames, int len, const iq_carrier_t* par, iq_stream_t stream);
+/* Blind equaliser (csrc/equaliser.hip): an L-tap complex filter per frame, found by block constant-modulus descent (CMA) on the
+ * frame itself, and the filter.  It sits behind the receiver and undoes what a static multipath channel (iq_waveform_t.n_taps)
+ * leaves between the symbols.  x and out are fp32 frames of len complex points, planar = 0: [n_frames, len, 2], the receiver's
+ * output; planar = 1: [n_frames, 2, len], the front ends' input (as iq_carrier_t); z[n] = I[n] + j Q[n], and z[n] = 0 outside
+ * [0, len).  L = taps weights w[l], l = 0 .. L-1, centre c = L / 2 (integer division).
+ *   Filter:  y[n] = sum_l w[l] z[n + c - l], n = 0 .. len-1: per output one fp32 fmaf chain from +0 over l ascending, the real part
+ *            taking + Re z Re w then - Im z Im w, the imaginary part + Re z Im w then + Im z Re w (four fmaf per tap, no
+ *            separately rounded product).
+ *   IQ_EQ_CMA.  w^0 = par->w0[frame] (DEVICE fp32 [n_frames, L, 2]), or the unit spike at c (w[c] = 1, every other weight 0) when
+ *            w0 is NULL.  For t = 0 .. iters-1, with y from w^t:
+ *              d[n] = (fmaf(Im y, Im y, Re y * Re y)) - R         R = modulus, the dispersion constant E|a|^4 / E|a|^2 of the
+ *              e[n] = (Re y * d, Im y * d)                        constellation: 1 for PSK at unit power
+ *              G[l] = sum_n conj(z[n + c - l]) e[n]:  Re += Re z Re e, then Im z Im e;  Im += Re z Im e, then - Im z Re e, all fmaf
+ *              w^{t+1}[l] = fmaf(-mu, G[l] / (float)len, w^t[l]), the real and the imaginary word alike (g = G / len)
+ *            Every sum over n runs in one order: thread n % 256 its outputs n ascending (a chain of fmaf from +0), then the
+ *            wave's butterfly (xor 32, 16, 8, 4, 2, 1), then the four wave sums ((s0 + s1) + s2) + s3.  Then out = y from
+ *            w^iters.  The input is expected at unit mean power (iq_receiver_t.normalise = 1): R is in its units.
+ *   IQ_EQ_GIVEN.  w = par->w[frame]; only the filter runs.  iters, mu and w0 are checked as below and not read otherwise;
+ *            modulus is used: est[1] = J(w) is formed with it.
+ * Outputs: out; w_out: NULL or fp32 [n_frames, L, 2] = w^iters (GIVEN: w); est: NULL or fp32 [n_frames, 4] = {J(w^0), J(w^iters),
+ * sum_l |w[l]|^2 (l ascending, fmaf(Im, Im, fmaf(Re, Re, acc))), the index of the largest fmaf(Im w, Im w, Re w * Re w), the
+ * lowest on ties}, w = w^iters in the last two; J(w) = (sum_n d[n]^2) / (float)len with y from w, the sum as fmaf(d, d, acc) in
+ * the order above.  With iters = 0, J(w^0) = J(w^iters); under GIVEN est[0] is NaN.  NaNs are not special-cased: they propagate
+ * within their frame only.  No atomics: two runs agree bit for bit, and a frame's outputs depend on neither n_frames nor its
+ * position.  Nothing is allocated, the host is not synchronised; the iters steps run inside one launch.
+ * iq_frames_equalise_bwd: dx[m] = sum_l conj(w[l]) dout[m - c + l], dout zero outside the frame; per output an fmaf chain over l
+ * ascending, Re: + Re d Re w then + Im d Im w, Im: + Im d Re w then - Re d Im w.  w = par->w[frame] whatever par->mode says: the
+ * adjoint with the weights held fixed (pass the forward's w_out), as the receiver holds its timing and the carrier its estimate.
+ * One workgroup per frame.  LDS: the frame as two planes, each with 32 zeros on either side, w, and the wave sums: at most 65.8 KB.
+ * IQ_STATUS_ARG before any launch, outputs untouched: NULL x / out / dout / dx / par; taps < 1; len < 1; iters < 0; mu or modulus
+ * not finite, mu < 0; planar outside {0,1}; mode outside IQ_EQ_*; x / out / dout / dx not 8-byte (planar = 0) or 4-byte
+ * (planar = 1) aligned, any other pointer not 4-byte aligned; NULL w with IQ_EQ_GIVEN or in the backward.
+ * IQ_STATUS_UNSUPPORTED: taps > 32, iters > 4096, len * 8 bytes above 64 KB.  n_frames <= 0: success, nothing is launched. */
+enum { IQ_EQ_GIVEN = 0, IQ_EQ_CMA = 1 };
+typedef struct iq_equaliser {
+  int taps;       /* L in [1,32] */
+  int iters;      /* CMA steps in [0,4096] */
+  int planar;     /* 0: x,out [n,len,2]; 1: [n,2,len] */
+  int mode;       /* IQ_EQ_* */
+  float mu;       /* step size, >= 0 */
+  float modulus;  /* R */
+  const float* w;   /* DEVICE fp32 [n,L,2]: IQ_EQ_GIVEN and the backward */
+  const float* w0;  /* DEVICE fp32 [n,L,2] or NULL (the unit spike at c): IQ_EQ_CMA */
+} iq_equaliser_t;
+int iq_frames_equalise(const float* x, float* out, float* w_out /*NULL or [n,L,2]*/, float* est /*NULL or [n,4]*/, int n_frames,
+                       int len, const iq_equaliser_t* par, iq_stream_t stream);
+int iq_frames_equalise_bwd(const float* dout, float* dx, int n_frames, int len, const iq_equaliser_t* par, iq_stream_t stream);
 int iq_patchify(const float* src, void* patches, int kind, int B, int C, int H, int W, int p, int Kpad,
                 iq_stream_t stream);
 int iq_cls_rows(const float* cls, const float* pe, void* x0, int B, int S, int D, const iq_dropout_t* drop,

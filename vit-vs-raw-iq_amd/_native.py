@@ -72,6 +72,11 @@ class Carrier(C.Structure):
                 ("fth", C.c_void_p)]
 
 
+class Equaliser(C.Structure):
+    _fields_ = [("taps", C.c_int), ("iters", C.c_int), ("planar", C.c_int), ("mode", C.c_int), ("mu", C.c_float),
+                ("modulus", C.c_float), ("w", C.c_void_p), ("w0", C.c_void_p)]
+
+
 class Cyclic(C.Structure):
     _fields_ = [("n_fft", C.c_int), ("hop", C.c_int), ("pad", C.c_int), ("columns", C.c_int), ("kind", C.c_int),
                 ("mode", C.c_int), ("inv_norm", C.c_float), ("floor", C.c_float), ("scale", C.c_float), ("shift", C.c_float)]
@@ -167,6 +172,8 @@ SIGNATURES = {
     "iq_frames_constellation_bwd": (_I, [_P, _P, _P, _P, _I, _I, C.POINTER(Constellation), _P]),
     "iq_frames_carrier": (_I, [_P, _P, _P, _P, _P, _I, _I, C.POINTER(Carrier), _P]),
     "iq_frames_carrier_bwd": (_I, [_P, _P, _I, _I, C.POINTER(Carrier), _P]),
+    "iq_frames_equalise": (_I, [_P, _P, _P, _P, _I, _I, C.POINTER(Equaliser), _P]),
+    "iq_frames_equalise_bwd": (_I, [_P, _P, _I, _I, C.POINTER(Equaliser), _P]),
     "iq_patchify": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "iq_cls_rows": (_I, [_P, _P, _P, _I, _I, _I, C.POINTER(Dropout), _P]),
     "iq_embed_bwd_gather": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, C.POINTER(Dropout), _I, _P]),

@@ -17,11 +17,12 @@ constellation's own M-th-power angle (a diagonal QPSK comes out on the axes).  T
   dft_tables(n1, n2) -> (t1 [2, n1, n1], t2 [2, n2, n2], tw [2, n1 * n2]) fp32
   dft_factors(n_dft) -> (n1, n2)                     default_n_dft(length) -> N
   Carrier(length, order, n_dft, f_max, refine, layout, tables, device)      carrier(x, fth) -> out [, est, fth, power]
-  Synchronised(front, carrier)                                             a FrontEnd: front(carrier(x)); goes where spectrogram= does
+  Synchronised(front, carrier, equaliser=None)                             a FrontEnd: front(carrier(x)), or front(carrier(
+                                                                           equaliser(x))); goes where spectrogram= does
   carrier_reference(x, tables, order, ...) -> out, est, fth, power         carrier_reference_bwd(dout, fth, planar) -> dx
 
-Not here: a hook for the `rawiq` layout of SynthStream / DeviceInputPipeline, a FrameSynth wrapper, choosing M per frame, and
-decision-directed tracking.
+For the `rawiq` layout there is receiver.ReceivedSynth(shaped, receiver, equaliser=, carrier=), a FrameSynth whose frames have
+passed through the stages.  Not here: choosing M per frame, and decision-directed tracking.
 """
 from __future__ import annotations
 
@@ -33,6 +34,7 @@ import torch
 
 from . import _native as N
 from ._args import _flag, _index, _number
+from .equaliser import Equaliser
 from .frontend import MAX_LENGTH, FrontEnd, _host
 
 ORDERS = (1, 2, 4, 8)
@@ -270,12 +272,14 @@ class _CarrierFn(torch.autograd.Function):
 
 class Synchronised(FrontEnd):
     """An image front end behind a carrier recovery: `front(carrier(x))`, a FrontEnd itself, so it goes wherever `spectrogram=`
-    is accepted.  height, width, channels, length and differentiability are those of `front`; `fit` fits `front` on the
-    derotated subset.  The carrier must be planar (the front ends' layout) and of the front end's length."""
+    is accepted.  With equaliser= the blind equaliser runs first: `front(carrier(equaliser(x)))` (CMA leaves a rotation, which
+    the carrier then takes out).  height, width, channels, length and differentiability are those of `front`; `fit` fits `front`
+    on the subset after both stages.  The carrier and the equaliser must be planar (the front ends' layout) and of the front
+    end's length."""
 
     reference = "carrier_reference"
 
-    def __init__(self, front, carrier):
+    def __init__(self, front, carrier, equaliser=None):
         if not isinstance(front, FrontEnd):
             raise TypeError(f"front must be a FrontEnd (Spectrogram, CyclicSpectrum, Constellation), got {type(front).__name__}")
         if not isinstance(carrier, Carrier):
@@ -284,8 +288,15 @@ class Synchronised(FrontEnd):
             raise ValueError(f"the front ends read planar (B, 2, length) frames: the carrier's layout is {carrier.layout!r}")
         if carrier.length != front.length:
             raise ValueError(f"the carrier was built for frames of {carrier.length} samples, the front end for {front.length}")
+        if equaliser is not None:
+            if not isinstance(equaliser, Equaliser):
+                raise TypeError(f"equaliser must be an Equaliser or None, got {type(equaliser).__name__}")
+            if not equaliser.planar:
+                raise ValueError(f"the front ends read planar (B, 2, length) frames: the equaliser's layout is {equaliser.layout!r}")
+            if equaliser.length != front.length:
+                raise ValueError(f"the equaliser was built for frames of {equaliser.length} samples, the front end for {front.length}")
         super().__init__(front.length)
-        self.front, self.carrier = front, carrier
+        self.front, self.carrier, self.equaliser = front, carrier, equaliser
         self.height, self.width, self.channels = front.height, front.width, front.channels
 
     @property
@@ -297,17 +308,20 @@ class Synchronised(FrontEnd):
 
     def __call__(self, x):
         """x: device (B, 2, length) fp32 -> the front end's image of the derotated frames, on the current stream, no host
-        synchronisation; differentiable with respect to x where `front` is (the carrier estimate held fixed)."""
-        return self.front(self.carrier(x))
+        synchronisation; differentiable with respect to x where `front` is (the carrier estimate and the equaliser's weights
+        held fixed)."""
+        return self.front(self.carrier(x if self.equaliser is None else self.equaliser(x)))
 
     def fit(self, x_subset):
-        """front.fit on the derotated subset.  -> self."""
+        """front.fit on the (equalised and) derotated subset.  -> self."""
         with torch.no_grad():
-            self.front.fit(self.carrier(x_subset))
+            self.front.fit(self.carrier(x_subset if self.equaliser is None else self.equaliser(x_subset)))
         return self
 
     def __repr__(self):
-        return f"Synchronised({self.front!r}, {self.carrier!r})"
+        if self.equaliser is None:
+            return f"Synchronised({self.front!r}, {self.carrier!r})"
+        return f"Synchronised({self.front!r}, {self.carrier!r}, equaliser={self.equaliser!r})"
 
 
 # ---- the host definition

@@ -49,18 +49,6 @@ struct CrArgs {
   int s1;               // row stride of Bm: n1 + 1
 };
 
-__device__ __forceinline__ float2 load_sample(const float* fr, int len, int planar, int n) {
-  return planar ? make_float2(fr[n], fr[len + n]) : reinterpret_cast<const float2*>(fr)[n];
-}
-__device__ __forceinline__ void store_sample(float* fr, int len, int planar, int n, float2 v) {
-  if (planar) {
-    fr[n] = v.x;
-    fr[len + n] = v.y;
-  } else {
-    reinterpret_cast<float2*>(fr)[n] = v;
-  }
-}
-
 // z^M by log2 M squarings, each a rotate() of the value by itself
 __device__ __forceinline__ float2 mth_power(float2 z, int order) {
   for (int m = 1; m < order; m <<= 1) z = rotate(z, z.x, z.y);

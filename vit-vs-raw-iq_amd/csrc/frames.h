@@ -6,6 +6,7 @@
 //                 synth_lists_ok, pack_synth_lists
 //   channelizers  f32x16, acc_row, frame_floats, window_start, stage_frame, channel_step, overlap_add, power, scale_shift,
 //                 image_value, fft_size_ok
+//   symbol stages load_sample, store_sample
 #pragma once
 #include <math.h>
 
@@ -148,6 +149,19 @@ __device__ __forceinline__ void store_frame(float* dst, const float2* fr, int le
       reinterpret_cast<float2*>(dst)[2 * p] = make_float2(v.x, v.y);
       if (2 * p + 1 < len) reinterpret_cast<float2*>(dst)[2 * p + 1] = make_float2(v.z, v.w);
     }
+  }
+}
+
+// ---- symbol stages (carrier.hip, equaliser.hip): sample n of a frame in either layout, planar [2][len] or interleaved [len][2]
+__device__ __forceinline__ float2 load_sample(const float* fr, int len, int planar, int n) {
+  return planar ? make_float2(fr[n], fr[len + n]) : reinterpret_cast<const float2*>(fr)[n];
+}
+__device__ __forceinline__ void store_sample(float* fr, int len, int planar, int n, float2 v) {
+  if (planar) {
+    fr[n] = v.x;
+    fr[len + n] = v.y;
+  } else {
+    reinterpret_cast<float2*>(fr)[n] = v;
   }
 }
 

@@ -12,7 +12,7 @@ the tests compare against.
   mf_table(alpha, sps, span, n_frac) -> fp32 [n_frac, sps * span + 1]
   Receiver(sps, span, alpha, n_frac, timing, normalise, table, device)   (raw (B, len, 2), u) -> (B, len // sps, 2)
   Receiver.for_synth(shaped, **kw)                                        sps, span, alpha, n_frac = n_phase of a ShapedSynth
-  ReceivedSynth(shaped, receiver)                                         a FrameSynth of length len // sps: goes into SynthStream
+  ReceivedSynth(shaped, receiver, equaliser=None, carrier=None)           a FrameSynth of length len // sps: goes into SynthStream
   receiver_reference(raw, table, sps, mode, u, normalise) -> sym, est, energy        receiver_reference_bwd(...) -> dx
   transmitted_index(shaped, q, u)                                         the transmitted symbol output 0 sits on
 """
@@ -213,10 +213,11 @@ class _ReceiveFn(torch.autograd.Function):
 
 class ReceivedSynth(FrameSynth):
     """A ShapedSynth seen through a Receiver: a FrameSynth whose frames are the received symbols, length = shaped.length // sps,
-    labels, SNRs and keying those of `shaped`.  Goes into SynthStream, train_on_stream, impair and
-    evaluate_model_with_confusion as it is."""
+    labels, SNRs and keying those of `shaped`.  equaliser= (an equaliser.Equaliser) and carrier= (a carrier.Carrier), each of
+    layout (B, length, 2) and of this length, then run on the symbols in that order.  Goes into SynthStream, train_on_stream,
+    impair and evaluate_model_with_confusion as it is."""
 
-    def __init__(self, shaped, receiver):
+    def __init__(self, shaped, receiver, equaliser=None, carrier=None):
         if not isinstance(shaped, ShapedSynth):
             raise TypeError(f"shaped must be a ShapedSynth, got {type(shaped).__name__}")
         if not isinstance(receiver, Receiver):
@@ -229,22 +230,41 @@ class ReceivedSynth(FrameSynth):
         self.class_names, self.descriptors, self.points = shaped.class_names, shaped.descriptors, shaped.points
         self.snrs_db, self.seed, self.balanced, self.device = shaped.snrs_db, shaped.seed, shaped.balanced, shaped.device
         self.length = receiver.n_out(shaped.length)
+        from .carrier import Carrier             # (carrier.py imports the front ends, which import synth.py as this file does)
+        from .equaliser import Equaliser
+        for stage, cls, what in ((equaliser, Equaliser, "equaliser"), (carrier, Carrier, "carrier")):
+            if stage is None:
+                continue
+            if not isinstance(stage, cls):
+                raise TypeError(f"{what} must be {'an' if what[0] == 'e' else 'a'} {cls.__name__} or None, got {type(stage).__name__}")
+            if stage.planar:
+                raise ValueError(f"the receiver writes (B, length, 2) frames: the {what}'s layout is {stage.layout!r}")
+            if stage.length != self.length:
+                raise ValueError(f"the {what} was built for frames of {stage.length} symbols, the receiver gives {self.length}")
+        self.equaliser, self.carrier = equaliser, carrier
+
+    def _stages(self, sym):
+        if self.equaliser is not None:
+            sym = self.equaliser(sym)
+        return sym if self.carrier is None else self.carrier(sym)
 
     def struct(self, *args, **kw):
         raise TypeError("a ReceivedSynth has no iq_synth_t of its own: see .shaped.struct and .receiver.struct")
 
     def generate(self, n, frame_base=0, stream=0, return_est=False, **kw):
-        """Frames [frame_base, frame_base + n) of `stream` of the ShapedSynth, received -> (sym (n, len // sps, 2) fp32, y, z),
-        then what ShapedSynth.generate appends for its own keywords, then est (n, 4) with return_est."""
+        """Frames [frame_base, frame_base + n) of `stream` of the ShapedSynth, received (then equalised, then derotated, where
+        those stages were given) -> (sym (n, len // sps, 2) fp32, y, z), then what ShapedSynth.generate appends for its own
+        keywords, then the receiver's est (n, 4) with return_est."""
         return_est = _flag(return_est, "return_est")
         raw, *rest = self.shaped.generate(n, frame_base, stream, **kw)
         if return_est:
             sym, est = self.receiver(raw, return_est=True)
-            return (sym, *rest, est)
-        return (self.receiver(raw), *rest)
+            return (self._stages(sym), *rest, est)
+        return (self._stages(self.receiver(raw)), *rest)
 
     def __repr__(self):
-        return f"ReceivedSynth({self.shaped!r}, {self.receiver!r})"
+        more = "".join(f", {k}={v!r}" for k, v in (("equaliser", self.equaliser), ("carrier", self.carrier)) if v is not None)
+        return f"ReceivedSynth({self.shaped!r}, {self.receiver!r}{more})"
 
 
 def _host(a):
