@@ -824,7 +824,13 @@ __global__ __launch_bounds__(NW * 64, 2) void ffn_chain_bwd_kernel(const FfnChai
   #pragma unroll
         for (int e = 0; e < 8; ++e) { ag[v][e] = 0.f; ab[v][e] = 0.f; }
       }
-  #pragma unroll
+      // A LOOP, not RW / 8 unrolled copies: unrolled, the scheduler moved the row addresses and loads of all the passes to the
+      // front (five 64-bit pointers, offsets of the prologue and the fragment offsets of the dA product went to scratch: 6 to 68
+      // registers with 32-row waves at D = 192, and the spill stores and reloads are counted by the same vmcnt as the ring's
+      // hand-counted waits; unrolled by two still 15).  Rolled, a pass needs its own rows only: MODE 0 / 1 hold 248 / 254
+      // registers and use no scratch, MODE 2 spills 3 (tests/test_chain_isa_cpu.py); 68.1 -> 64.4 us per cfg B launch
+      // (profiles/chain_spills.txt).  Same arithmetic in the same order: every output keeps its bits.
+  #pragma unroll 1
       for (int it = 0; it < RW / 8; ++it) {
         const int rl = it * 8 + rsub;
         const long row = row0 + rl;
