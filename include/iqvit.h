@@ -749,6 +749,57 @@ typedef struct iq_equaliser {
 int iq_frames_equalise(const float* x, float* out, float* w_out /*NULL or [n,L,2]*/, float* est /*NULL or [n,4]*/, int n_frames,
                        int len, const iq_equaliser_t* par, iq_stream_t stream);
 int iq_frames_equalise_bwd(const float* dout, float* dx, int n_frames, int len, const iq_equaliser_t* par, iq_stream_t stream);
+/* Likelihood classifier (csrc/likelihood.hip): the classical baseline of modulation classification.  For every frame and every
+ * candidate constellation the log-likelihood of the frame's symbols as independent draws from the constellation in complex
+ * Gaussian noise of known variance, over a table of carrier rotations (the phase is unknown), and the class of the largest.
+ * x: fp32 frames of len symbols at one sample per symbol, planar = 0: [n_frames, len, 2], what the generators, the receiver and
+ * the equaliser write; planar = 1: [n_frames, 2, len], what the carrier recovery writes; y[n] = I[n] + j Q[n].  sigma2[b]: the
+ * noise variance E|w|^2 of frame b (both components together); gain[b]: the amplitude a of the constellation in the frame.
+ * Classes are those of iq_synth_t with kind 0 only: class c has the M_c = count points s_k = points[offset + k].  rot[r] =
+ * (c_r, s_r) is taken as two plain numbers (nothing is normalised).  All arithmetic is fp32, every operation rounded once, in
+ * this order; fmaf is the fused multiply-add, exp2 / log2 the device's base-2 instructions (v_exp_f32, v_log_f32: 1 ulp).
+ *   per frame      q = 1 / sigma2[b] (IEEE division);  q2 = q * LOG2E;  a = gain[b] (1 when gain is NULL);
+ *                  p_k = (a * Re s_k, a * Im s_k);  1/M = 1 / (float)M_c (IEEE division)
+ *   per rotation   y' = (fmaf(c_r, Re y, s_r * Im y), fmaf(c_r, Im y, -(s_r * Re y)))
+ *   per symbol     d_k = fmaf(Im y' - Im p_k, Im y' - Im p_k, (Re y' - Re p_k) * (Re y' - Re p_k)): the difference form, which does
+ *                  not cancel at high SNR as |y|^2 + |s|^2 - 2 Re(y conj s) does;  d_min = min_k d_k;
+ *                  S = sum_k exp2(q2 * (d_min - d_k)), k ascending from +0;  l_n = fmaf(-q, d_min, LN2 * log2(S * (1/M)))
+ *                  (= -q d_min + log((1/M) sum_k exp(-q (d_k - d_min))): with d_min taken out every term is finite and S >= 1,
+ *                  so a wrong class at 30 dB does not underflow to log 0)
+ *   L[b, c, r]     = sum_n l_n: lane n % 64 of a wave adds its symbols n ascending from +0, then the wave's butterfly
+ *                  (xor 32, 16, 8, 4, 2, 1)
+ *   loglik[b, c]   IQ_LIK_MAX (GLRT):  max_r L, best_rot the first r that attains it (r ascending; a NaN is never larger nor beaten)
+ *                  IQ_LIK_MEAN (ALRT): m + LN2 * log2(T * (1 / (float)R)), m = max_r L, T = sum_r exp2(LOG2E * (L[r] - m)), r
+ *                  ascending from +0: the log of the mean over the rotations
+ *   pred[b]        the first c with the largest loglik[b, c] (c ascending)
+ * The term -len log(pi sigma2), common to all classes, is LEFT OUT: loglik orders the classes of one frame and is not a density.
+ * A sigma2[b] that is not a positive finite number is data, not an argument: that frame gets NaN in loglik and rot_ll and -1 in
+ * best_rot and pred, and no other frame is touched.  Other NaNs are not special-cased: they stay within their frame.
+ * Outputs: loglik fp32 [n_frames, C]; rot_ll: NULL or fp32 [n_frames, C, R] = L; best_rot: NULL or int32 [n_frames, C]; pred:
+ * NULL or int32 [n_frames], written by a second small launch.  One workgroup per (frame, class) runs all R rotations: no atomics,
+ * no workspace, two runs agree bit for bit and a frame's outputs depend on neither n_frames nor its position.  LDS 17 KB.
+ * There is no backward: nothing downstream differentiates through a log-likelihood.
+ * IQ_STATUS_ARG before any HIP call, outputs untouched: NULL x / sigma2 / loglik / par / points / classes / rot; len < 1; n_classes
+ * or n_rot < 1; planar outside {0,1}; mode outside IQ_LIK_*; a class with kind != 0, count < 1, offset < 0 or offset + count past
+ * the int range; x not 8-byte (planar = 0) or 4-byte (planar = 1) aligned, points not 8-byte, any other pointer not 4-byte aligned.
+ * IQ_STATUS_UNSUPPORTED: C > 64, R > 256, a class that ends behind point 2048 of the table (the table's own size is not passed:
+ * 2048 points, 16 KB of LDS, is the most a class may reach), len * 8 bytes above 64 KB (the frame kernels' limit), n_frames * C
+ * above 2^31 - 1.  n_frames <= 0: success, nothing is launched. */
+enum { IQ_LIK_MAX = 0, IQ_LIK_MEAN = 1 };
+typedef struct iq_likelihood {
+  const float* points;                 /* DEVICE fp32 (re, im) pairs, as iq_synth_t.points */
+  const iq_synth_class_t* classes;     /* HOST array, copied into the launch; every kind must be 0 */
+  int n_classes;                       /* C in [1, 64] */
+  const float* rot;                    /* DEVICE fp32 [R, 2] = (cos, sin): plain numbers to the kernel */
+  int n_rot;                           /* R in [1, 256] */
+  int planar;                          /* 0: x [n, len, 2]; 1: [n, 2, len] */
+  int mode;                            /* IQ_LIK_*: over the rotations, the maximum (GLRT) or the log of the mean (ALRT) */
+  const float* gain;                   /* DEVICE fp32 [n] or NULL (= 1): amplitude a of the signal in the frame */
+} iq_likelihood_t;
+int iq_frames_likelihood(const float* x, const float* sigma2 /*[n]*/, float* loglik /*[n, C]*/,
+                         float* rot_ll /*NULL or [n, C, R]*/, int* best_rot /*NULL or [n, C]*/,
+                         int* pred /*NULL or [n]*/, int n_frames, int len,
+                         const iq_likelihood_t* par, iq_stream_t stream);
 int iq_patchify(const float* src, void* patches, int kind, int B, int C, int H, int W, int p, int Kpad,
                 iq_stream_t stream);
 int iq_cls_rows(const float* cls, const float* pe, void* x0, int B, int S, int D, const iq_dropout_t* drop,

@@ -25,6 +25,8 @@ Import name: `vit_vs_raw_iq_amd` (the directory name contains hyphens; the repo-
                differentiable (Carrier), and Synchronised, a front end behind it
   equaliser -- blind equaliser on the device: block constant-modulus descent of an L-tap filter per frame, differentiable
                (Equaliser); goes in front of the carrier recovery (Synchronised(equaliser=), ReceivedSynth(equaliser=, carrier=))
+  likelihood -- likelihood classifier on the device: the classical AMC baseline over the candidate constellations and a table of
+               carrier rotations (LikelihoodClassifier, noise_for); evaluation.evaluate_likelihood_with_confusion writes its report
   _native   -- ctypes binding of include/iqvit.h  (libiqvit.so; no fallback)
   ViT.models.amc_transformer / transformer_rawIQ.models.transformer_rawIQ
             -- import paths used by the reference's scripts (hyperparameter_tuning.py:19,37)
@@ -47,6 +49,7 @@ from .receiver import (Receiver, ReceivedSynth, mf_table, receiver_reference, re
                        transmitted_index)
 from .carrier import Carrier, Synchronised, carrier_reference, carrier_reference_bwd, dft_tables
 from .equaliser import Equaliser, equaliser_reference, equaliser_reference_bwd
+from .likelihood import LikelihoodClassifier, likelihood_reference, noise_for
 
 __all__ = ["AMCTransformerViT", "AMCTransformerRawIQ", "EncoderViT", "EncoderRawIQ", "EncoderLayer", "LayerNorm",
            "MultiHeadAttention", "PositionwiseFeedForward", "ScaleDotProductAttention", "PatchEmbedding",
@@ -57,4 +60,5 @@ __all__ = ["AMCTransformerViT", "AMCTransformerRawIQ", "EncoderViT", "EncoderRaw
            "ShapedSynth", "rrc_table", "gmsk_table", "waveform_reference", "Receiver", "ReceivedSynth", "mf_table", "receiver_reference",
            "receiver_reference_bwd", "transmitted_index", "CyclicSpectrum", "cyclic_reference", "cyclic_reference_bwd",
            "Constellation", "constellation_reference", "constellation_reference_bwd", "Carrier", "Synchronised", "carrier_reference",
-           "carrier_reference_bwd", "dft_tables", "Equaliser", "equaliser_reference", "equaliser_reference_bwd"]
+           "carrier_reference_bwd", "dft_tables", "Equaliser", "equaliser_reference", "equaliser_reference_bwd",
+           "LikelihoodClassifier", "likelihood_reference", "noise_for"]

@@ -52,27 +52,29 @@ def classification_report_text(cm: np.ndarray, class_names: Sequence[str], digit
     return report
 
 
+def report_text(prefix: str, overall: float, snr_acc: Dict[int, float], body: str) -> str:
+    """The report file's text: the layout compare_models.py parses."""
+    text = f"Classification Report - {prefix.capitalize()} Set\n"
+    text += "=" * 80 + "\n\n"
+    text += f"Overall Accuracy: {overall * 100:.2f}%\n\n"
+    text += "Accuracy by SNR:\n"
+    for snr, acc in snr_acc.items():
+        text += f"  SNR {snr:+3d} dB: {acc * 100:.2f}%\n"
+    text += "\n" + "=" * 80 + "\n\n"
+    return text + body
+
+
 def write_report(path: Path, prefix: str, overall: float, snr_acc: Dict[int, float], body: str) -> None:
     path.parent.mkdir(parents=True, exist_ok=True)
     with open(path, "w") as f:
-        f.write(f"Classification Report - {prefix.capitalize()} Set\n")
-        f.write("=" * 80 + "\n\n")
-        f.write(f"Overall Accuracy: {overall * 100:.2f}%\n\n")
-        f.write("Accuracy by SNR:\n")
-        for snr, acc in snr_acc.items():
-            f.write(f"  SNR {snr:+3d} dB: {acc * 100:.2f}%\n")
-        f.write("\n" + "=" * 80 + "\n\n")
-        f.write(body)
+        f.write(report_text(prefix, overall, snr_acc, body))
 
 
-@torch.no_grad()
-def evaluate_model_with_confusion(model: torch.nn.Module, dataloader: Iterable, device: torch.device,
-                                  class_names: List[str], save_dir: Path, prefix: str = "test") -> Dict:
-    """`dataloader` yields (inputs, labels, snrs) like the reference's DataLoader (V/training/utils.py:311)."""
-    device = torch.device(device)
+def _evaluate_with_confusion(predict, dataloader: Iterable, device: torch.device, class_names: List[str], save_dir: Path,
+                             prefix: str) -> Dict:
+    """What the two evaluations below share: predict(x, y, z) -> (B,) class indices on the device for every batch of
+    `dataloader`, the K x K confusion matrices accumulated on the device, the report file, the result dictionary."""
     K = len(class_names)
-    was_training = model.training
-    model.eval()
     cm = torch.zeros(K * K, dtype=torch.int64, device=device)
     cm_snr = {s: torch.zeros(K * K, dtype=torch.int64, device=device) for s in TARGET_SNRS}
     preds, labels_all, snrs_all = [], [], []
@@ -80,7 +82,7 @@ def evaluate_model_with_confusion(model: torch.nn.Module, dataloader: Iterable, 
         x = x.to(device, non_blocking=True)
         y = y.to(device, non_blocking=True).long()
         z = z.to(device, non_blocking=True).float()
-        p = model(x).argmax(1)
+        p = predict(x, y, z)
         idx = y * K + p
         cm += torch.bincount(idx, minlength=K * K)
         for s in TARGET_SNRS:
@@ -89,7 +91,6 @@ def evaluate_model_with_confusion(model: torch.nn.Module, dataloader: Iterable, 
         preds.append(p)
         labels_all.append(y)
         snrs_all.append(z)
-    model.train(was_training)
     cm_np = cm.view(K, K).cpu().numpy()                       # single host transfer
     overall = float(np.trace(cm_np) / max(cm_np.sum(), 1))
     snr_acc = {}
@@ -104,3 +105,28 @@ def evaluate_model_with_confusion(model: torch.nn.Module, dataloader: Iterable, 
             "predictions": torch.cat(preds).cpu().numpy() if preds else np.zeros(0, np.int64),
             "labels": torch.cat(labels_all).cpu().numpy() if labels_all else np.zeros(0, np.int64),
             "snrs": torch.cat(snrs_all).cpu().numpy() if snrs_all else np.zeros(0, np.float32)}
+
+
+@torch.no_grad()
+def evaluate_model_with_confusion(model: torch.nn.Module, dataloader: Iterable, device: torch.device,
+                                  class_names: List[str], save_dir: Path, prefix: str = "test") -> Dict:
+    """`dataloader` yields (inputs, labels, snrs) like the reference's DataLoader (V/training/utils.py:311)."""
+    device = torch.device(device)
+    was_training = model.training
+    model.eval()
+    res = _evaluate_with_confusion(lambda x, y, z: model(x).argmax(1), dataloader, device, class_names, save_dir, prefix)
+    model.train(was_training)
+    return res
+
+
+@torch.no_grad()
+def evaluate_likelihood_with_confusion(clf, dataloader: Iterable, device: torch.device, class_names: List[str], save_dir: Path,
+                                       prefix: str = "test") -> Dict:
+    """The same evaluation and the same report file for a likelihood.LikelihoodClassifier: compare_models.py reads it as a
+    third column beside the two learned models.  `dataloader` yields (frames, labels, snrs) with UN-NORMALISED frames in the
+    classifier's layout, a unit-power signal plus noise at the finite SNR `snrs` (dB) as the generators emit them; labels index
+    `class_names`, which must be the classifier's classes."""
+    device = torch.device(device)
+    if list(class_names) != list(clf.class_names):
+        raise ValueError(f"class_names must be the classifier's classes {clf.class_names!r}, got {list(class_names)!r}")
+    return _evaluate_with_confusion(lambda x, y, z: clf.predict(x, snr_db=z), dataloader, device, class_names, save_dir, prefix)
