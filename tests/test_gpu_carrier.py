@@ -19,24 +19,11 @@ import torch
 
 import carrier_ref as R
 import constellation_ref as CR
-from frontend_gpu import GUARD, SENTINEL, bits, dev, guarded, guards_intact, on_device, same_bits
-from prof_names import kernel_launches
+from frontend_gpu import ISENT, abi_call, dev, on_device, same_bits
 
 pytestmark = pytest.mark.gpu
 
-ISENT = -77777
 IDENT = dict(i_mean=0.0, i_std=1.0, q_mean=0.0, q_std=1.0)
-
-
-def guarded_int(a, fill):
-    a = np.ascontiguousarray(a, dtype=np.int32)
-    buf = torch.full((a.size + 2 * GUARD,), fill, dtype=torch.int32, device=dev())
-    buf[GUARD:GUARD + a.size] = torch.from_numpy(a.reshape(-1)).to(dev())
-    return buf, buf[GUARD:GUARD + a.size]
-
-
-def int_guards_intact(buf, fill):
-    return bool((torch.cat([buf[:GUARD], buf[-GUARD:]]) == fill).all())
 
 
 def wrap32(v):
@@ -46,59 +33,30 @@ def wrap32(v):
 def forward(x, order, n1, n2, k_max=None, refine=0, planar=1, tables=None, fth=None, power=True, expect_kernel=True):
     """One guarded iq_frames_carrier call -> dict(out, est, fth, power) as numpy (float64 / int64)."""
     import vit_vs_raw_iq_amd._native as N
-    L = N.lib()
     x = np.ascontiguousarray(x, dtype=np.float32)
     B, length, Nd = x.shape[0], x.shape[2] if planar else x.shape[1], n1 * n2
     given = fth is not None
-    xb, xv = guarded(x, np.nan)
-    tabs = [guarded(t, np.nan) for t in tables] if tables is not None else []
-    fb, fv = guarded_int(fth, ISENT) if given else (None, None)
-    ob, ov = guarded(np.full(x.shape, SENTINEL), SENTINEL)
-    eb, ev = guarded(np.full((B, 4), SENTINEL), SENTINEL)
-    qb, qv = guarded_int(np.full((B, 2), ISENT), ISENT)
-    pb, pv = guarded(np.full((B, Nd), SENTINEL), SENTINEL) if power and not given else (None, None)
-    par = N.Carrier(order=order, n1=n1, n2=n2, k_max=Nd // 2 if k_max is None else k_max, refine=refine, planar=planar,
-                    mode=0 if given else 1, t1=tabs[0][1].data_ptr() if tabs else None, t2=tabs[1][1].data_ptr() if tabs else None,
-                    tw=tabs[2][1].data_ptr() if tabs else None, fth=N.ptr(fv))
 
-    def run():
-        N.check(L.iq_frames_carrier(xv.data_ptr(), ov.data_ptr(), ev.data_ptr(), qv.data_ptr(), N.ptr(pv), B, length,
-                                    ctypes.byref(par), N.stream_handle()), "iq_frames_carrier")
-    if expect_kernel:
-        assert kernel_launches(L, run) == {"frames_carrier_kernel": 1}
-    else:
-        run()
-    torch.cuda.synchronize()
-    assert guards_intact(ob, SENTINEL) and guards_intact(eb, SENTINEL) and int_guards_intact(qb, ISENT)
-    assert pb is None or guards_intact(pb, SENTINEL)
-    assert guards_intact(xb, np.nan) and np.array_equal(bits(xv.cpu().numpy()), bits(x).reshape(-1))
-    for (buf, view), t in zip(tabs, tables or []):
-        assert guards_intact(buf, np.nan) and np.array_equal(bits(view.cpu().numpy()), bits(t).reshape(-1))
-    assert fb is None or (int_guards_intact(fb, ISENT) and np.array_equal(fv.cpu().numpy(), np.asarray(fth, np.int32).reshape(-1)))
-    return dict(out=ov.cpu().numpy().reshape(x.shape).astype(np.float64), est=ev.cpu().numpy().reshape(B, 4).astype(np.float64),
-                fth=qv.cpu().numpy().reshape(B, 2).astype(np.int64),
-                power=None if pv is None else pv.cpu().numpy().reshape(B, Nd).astype(np.float64))
+    def par(t1, t2, tw, f):
+        return N.Carrier(order=order, n1=n1, n2=n2, k_max=Nd // 2 if k_max is None else k_max, refine=refine, planar=planar,
+                         mode=0 if given else 1, t1=t1, t2=t2, tw=tw, fth=f)
+    out, est, fth_out, p = abi_call("iq_frames_carrier", "frames_carrier_kernel", (x,),
+                                    [x.shape, (B, 4), (np.int32, B, 2), (B, Nd) if power and not given else None], B, length, par,
+                                    expect_kernel, side=(*(tables or (None,) * 3), np.asarray(fth, np.int32) if given else None))
+    return dict(out=out.astype(np.float64), est=est.astype(np.float64), fth=fth_out.astype(np.int64),
+                power=None if p is None else p.astype(np.float64))
 
 
 def backward(dout, fth, planar=1, order=4, n1=32, n2=32):
     """One guarded iq_frames_carrier_bwd call -> dx float64."""
     import vit_vs_raw_iq_amd._native as N
-    L = N.lib()
     dout = np.ascontiguousarray(dout, dtype=np.float32)
     B, length = dout.shape[0], dout.shape[2] if planar else dout.shape[1]
-    db, dv = guarded(dout, np.nan)
-    fb, fv = guarded_int(fth, ISENT)
-    ob, ov = guarded(np.full(dout.shape, SENTINEL), SENTINEL)
-    par = N.Carrier(order=order, n1=n1, n2=n2, k_max=0, refine=0, planar=planar, mode=0, t1=None, t2=None, tw=None, fth=fv.data_ptr())
 
-    def run():
-        N.check(L.iq_frames_carrier_bwd(dv.data_ptr(), ov.data_ptr(), B, length, ctypes.byref(par), N.stream_handle()),
-                "iq_frames_carrier_bwd")
-    assert kernel_launches(L, run) == {"frames_carrier_bwd_kernel": 1}
-    torch.cuda.synchronize()
-    assert guards_intact(ob, SENTINEL) and guards_intact(db, np.nan) and int_guards_intact(fb, ISENT)
-    assert np.array_equal(bits(dv.cpu().numpy()), bits(dout).reshape(-1))
-    return ov.cpu().numpy().reshape(dout.shape).astype(np.float64)
+    def par(f):
+        return N.Carrier(order=order, n1=n1, n2=n2, k_max=0, refine=0, planar=planar, mode=0, t1=None, t2=None, tw=None, fth=f)
+    return abi_call("iq_frames_carrier_bwd", "frames_carrier_bwd_kernel", (dout,), dout.shape, B, length, par,
+                    side=(np.asarray(fth, np.int32),)).astype(np.float64)
 
 
 def in_layout(x, planar):

@@ -21,8 +21,7 @@ import pytest
 import torch
 
 import equaliser_ref as R
-from frontend_gpu import SENTINEL, bits, dev, guarded, guards_intact, on_device, same_bits
-from prof_names import kernel_launches
+from frontend_gpu import abi_call, bits, dev, on_device, same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -32,61 +31,27 @@ IDENT = dict(i_mean=0.0, i_std=1.0, q_mean=0.0, q_std=1.0)
 def forward(x, L, iters=0, mu=0.0, modulus=1.0, planar=0, w=None, w0=None, want=(True, True), expect_kernel=True):
     """One guarded iq_frames_equalise call -> dict(out, w, est) as float64 numpy.  w: IQ_EQ_GIVEN."""
     import vit_vs_raw_iq_amd._native as N
-    lib = N.lib()
     x = np.ascontiguousarray(x, dtype=np.float32)
     B, length = x.shape[0], x.shape[2] if planar else x.shape[1]
-    xb, xv = guarded(x, np.nan)
-    ins = [(xb, xv, x)]
-    ptrs = {}
-    for name, a in (("w", w), ("w0", w0)):
-        ptrs[name] = None
-        if a is not None:
-            a = np.ascontiguousarray(a, dtype=np.float32)
-            assert a.shape == (B, L, 2)
-            buf, view = guarded(a, np.nan)
-            ins.append((buf, view, a))
-            ptrs[name] = view.data_ptr()
-    ob, ov = guarded(np.full(x.shape, SENTINEL), SENTINEL)
-    wb, wv = guarded(np.full((B, L, 2), SENTINEL), SENTINEL) if want[0] else (None, None)
-    eb, ev = guarded(np.full((B, 4), SENTINEL), SENTINEL) if want[1] else (None, None)
-    par = N.Equaliser(taps=L, iters=iters, planar=planar, mode=0 if w is not None else 1, mu=mu, modulus=modulus, **ptrs)
+    assert all(a is None or np.shape(a) == (B, L, 2) for a in (w, w0))
 
-    def run():
-        N.check(lib.iq_frames_equalise(xv.data_ptr(), ov.data_ptr(), N.ptr(wv), N.ptr(ev), B, length, ctypes.byref(par),
-                                       N.stream_handle()), "iq_frames_equalise")
-    if expect_kernel:
-        assert kernel_launches(lib, run) == {f"frames_equalise_kernel<{L}>": 1}
-    else:
-        run()
-    torch.cuda.synchronize()
-    for buf in (ob, wb, eb):
-        assert buf is None or guards_intact(buf, SENTINEL)
-    for buf, view, a in ins:
-        assert guards_intact(buf, np.nan) and np.array_equal(bits(view.cpu().numpy()), bits(a).reshape(-1))
-    return dict(out=ov.cpu().numpy().reshape(x.shape).astype(np.float64),
-                w=None if wv is None else wv.cpu().numpy().reshape(B, L, 2).astype(np.float64),
-                est=None if ev is None else ev.cpu().numpy().reshape(B, 4).astype(np.float64))
+    def par(w, w0):
+        return N.Equaliser(taps=L, iters=iters, planar=planar, mode=0 if w is not None else 1, mu=mu, modulus=modulus, w=w, w0=w0)
+    got = abi_call("iq_frames_equalise", f"frames_equalise_kernel<{L}>", (x,),
+                   [x.shape, (B, L, 2) if want[0] else None, (B, 4) if want[1] else None], B, length, par, expect_kernel, side=(w, w0))
+    return dict(zip(("out", "w", "est"), (None if a is None else a.astype(np.float64) for a in got)))
 
 
 def backward(dout, w, planar=0, mode=0):
     """One guarded iq_frames_equalise_bwd call -> dx float64."""
     import vit_vs_raw_iq_amd._native as N
-    lib = N.lib()
     dout, w = np.ascontiguousarray(dout, dtype=np.float32), np.ascontiguousarray(w, dtype=np.float32)
     B, length, L = dout.shape[0], dout.shape[2] if planar else dout.shape[1], w.shape[1]
-    db, dv = guarded(dout, np.nan)
-    wb, wv = guarded(w, np.nan)
-    ob, ov = guarded(np.full(dout.shape, SENTINEL), SENTINEL)
-    par = N.Equaliser(taps=L, iters=3, planar=planar, mode=mode, mu=0.5, modulus=1.0, w=wv.data_ptr(), w0=None)
 
-    def run():
-        N.check(lib.iq_frames_equalise_bwd(dv.data_ptr(), ov.data_ptr(), B, length, ctypes.byref(par), N.stream_handle()),
-                "iq_frames_equalise_bwd")
-    assert kernel_launches(lib, run) == {f"frames_equalise_bwd_kernel<{L}>": 1}
-    torch.cuda.synchronize()
-    assert guards_intact(ob, SENTINEL) and guards_intact(db, np.nan) and guards_intact(wb, np.nan)
-    assert np.array_equal(bits(dv.cpu().numpy()), bits(dout).reshape(-1)) and np.array_equal(bits(wv.cpu().numpy()), bits(w).reshape(-1))
-    return ov.cpu().numpy().reshape(dout.shape).astype(np.float64)
+    def par(w):
+        return N.Equaliser(taps=L, iters=3, planar=planar, mode=mode, mu=0.5, modulus=1.0, w=w, w0=None)
+    return abi_call("iq_frames_equalise_bwd", f"frames_equalise_bwd_kernel<{L}>", (dout,), dout.shape, B, length, par,
+                    side=(w,)).astype(np.float64)
 
 
 def in_layout(x, planar):

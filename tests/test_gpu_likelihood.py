@@ -25,61 +25,30 @@ import pytest
 import torch
 
 import likelihood_ref as R
-from frontend_gpu import GUARD, SENTINEL, bits, dev, guarded, guards_intact, on_device, same_bits
+from frontend_gpu import ISENT, abi_call, bits, dev, on_device, same_bits
 from prof_names import kernel_launches
 
 pytestmark = pytest.mark.gpu
-
-ISENT = -12345
-
-
-def guarded_int(n):
-    buf = torch.full((n + 2 * GUARD,), ISENT, dtype=torch.int32, device=dev())
-    return buf, buf[GUARD:GUARD + n]
-
-
-def int_guards_intact(buf):
-    return bool((torch.cat([buf[:GUARD], buf[-GUARD:]]) == ISENT).all())
 
 
 def run(x, sigma2, gain, points, classes, rot, mode="max", planar=0, want=(True, True, True), expect_kernel=True):
     """One guarded iq_frames_likelihood call -> dict(loglik (B, C), L (B, C, R) float64, best_rot (B, C), pred (B,) int64)."""
     import vit_vs_raw_iq_amd._native as N
-    lib = N.lib()
-    x = np.array(x, dtype=np.float32, order="C")                                   # a copy: x may be read-only
+    x = np.asarray(x, dtype=np.float32)
     B, length = x.shape[0], x.shape[2] if planar else x.shape[1]
     Cn, Rn = len(classes), len(rot)
-    sigma2 = np.array(np.broadcast_to(np.asarray(sigma2, np.float32), (B,)))
-    ins = [guarded(a, np.nan) + (np.ascontiguousarray(a, dtype=np.float32),) for a in (x, sigma2, points, rot)]
-    gp = None
-    if gain is not None:
-        gain = np.array(np.broadcast_to(np.asarray(gain, np.float32), (B,)))
-        ins.append(guarded(gain, np.nan) + (np.ascontiguousarray(gain, dtype=np.float32),))
-        gp = ins[-1][1].data_ptr()
-    lb, lv = guarded(np.full((B, Cn), SENTINEL), SENTINEL)
-    tb, tv = guarded(np.full((B, Cn, Rn), SENTINEL), SENTINEL) if want[0] else (None, None)
-    bb, bv = guarded_int(B * Cn) if want[1] else (None, None)
-    pb, pv = guarded_int(B) if want[2] else (None, None)
+    sigma2 = np.broadcast_to(np.asarray(sigma2, np.float32), (B,))
+    gain = None if gain is None else np.broadcast_to(np.asarray(gain, np.float32), (B,))
     arr = (N.SynthClass * Cn)(*[N.SynthClass(0, int(o), int(m)) for o, m in classes])
-    par = N.Likelihood(points=ins[2][1].data_ptr(), classes=arr, n_classes=Cn, rot=ins[3][1].data_ptr(), n_rot=Rn, planar=planar,
-                       mode=("max", "mean").index(mode), gain=gp)
 
-    def call():
-        N.check(lib.iq_frames_likelihood(ins[0][1].data_ptr(), ins[1][1].data_ptr(), lv.data_ptr(), N.ptr(tv), N.ptr(bv), N.ptr(pv),
-                                         B, length, ctypes.byref(par), N.stream_handle()), "iq_frames_likelihood")
-    if expect_kernel:
-        assert kernel_launches(lib, call) == {"frames_likelihood_kernel": 1, **({"likelihood_decide_kernel": 1} if want[2] else {})}
-    else:
-        call()
-    torch.cuda.synchronize()
-    assert guards_intact(lb, SENTINEL) and (tb is None or guards_intact(tb, SENTINEL))
-    assert (bb is None or int_guards_intact(bb)) and (pb is None or int_guards_intact(pb))
-    for buf, view, a in ins:
-        assert guards_intact(buf, np.nan) and np.array_equal(bits(view.cpu().numpy()), bits(a).reshape(-1))
-    return dict(loglik=lv.cpu().numpy().reshape(B, Cn).astype(np.float64),
-                L=None if tv is None else tv.cpu().numpy().reshape(B, Cn, Rn).astype(np.float64),
-                best_rot=None if bv is None else bv.cpu().numpy().reshape(B, Cn).astype(np.int64),
-                pred=None if pv is None else pv.cpu().numpy().astype(np.int64))
+    def par(points, rot, gain):
+        return N.Likelihood(points=points, classes=arr, n_classes=Cn, rot=rot, n_rot=Rn, planar=planar,
+                            mode=("max", "mean").index(mode), gain=gain)
+    launches = {"frames_likelihood_kernel": 1, **({"likelihood_decide_kernel": 1} if want[2] else {})}
+    outs = [(B, Cn), (B, Cn, Rn) if want[0] else None, (np.int32, B, Cn) if want[1] else None, (np.int32, B) if want[2] else None]
+    got = abi_call("iq_frames_likelihood", launches, (x, sigma2), outs, B, length, par, expect_kernel, side=(points, rot, gain))
+    return dict(zip(("loglik", "L", "best_rot", "pred"),
+                    (None if a is None else a.astype(np.int64 if a.dtype == np.int32 else np.float64) for a in got)))
 
 
 def check_against(got, ref, tag):

@@ -22,7 +22,8 @@ import pytest
 import torch
 
 import spectrogram_ref as R
-from frontend_gpu import GUARD, SENTINEL, abi_call, bits, dev, on_device, same_bits, small_vit
+from frontend_gpu import (GUARD, ISENT, SENTINEL, abi_call, bits, dev, guarded, guarded_int, guards_intact, int_guards_intact,
+                          on_device, same_bits, small_vit)
 
 pytestmark = pytest.mark.gpu
 
@@ -364,3 +365,18 @@ def test_a_vit_trains_on_spectrograms_of_fresh_frames_and_the_curve_runs():
         impairment_curve(m, raw, y, stats, "cfo", values, spectrogram=Spectrogram(32, 32, 1024))
     with pytest.raises(ValueError):
         impairment_curve(m, raw, y, stats, "cfo", values, spectrogram=Spectrogram(64, 64, 1024))
+
+
+def test_the_scaffold_reports_a_written_guard_float_and_int():
+    """tests/frontend_gpu.py itself: one guard element overwritten (a torch assignment, no kernel of ours) is reported by
+    guards_intact / int_guards_intact, in front of the data and behind it, and an untouched pair reports nothing."""
+    for at in (GUARD - 1, GUARD + 4, 0, -1):
+        for fill in (np.nan, SENTINEL):
+            buf, view = guarded(np.arange(4.0), fill)
+            assert guards_intact(buf, fill) and view.tolist() == [0.0, 1.0, 2.0, 3.0]
+            buf[at] = 1.0
+            assert not guards_intact(buf, fill)
+        buf, view = guarded_int(np.arange(4))
+        assert int_guards_intact(buf) and view.tolist() == [0, 1, 2, 3] and buf.dtype == torch.int32
+        buf[at] = ISENT + 1
+        assert not int_guards_intact(buf)

@@ -1,4 +1,5 @@
-"""Argument checkers every generator, receiver and front end shares.  A leaf: nothing of the package is imported here."""
+"""Argument checkers, and the one limit (MAX_LENGTH), every generator, receiver, stage and front end shares.  A leaf: nothing
+of the package is imported here."""
 from __future__ import annotations
 
 import math
@@ -6,6 +7,7 @@ import numbers
 import operator
 
 _F32_MAX = 3.4028234663852886e38
+MAX_LENGTH = 8192            # one workgroup keeps one frame in LDS: len * 8 bytes <= 64 KB
 
 
 def _number(v, what):

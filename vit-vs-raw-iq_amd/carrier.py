@@ -33,9 +33,10 @@ import numpy as np
 import torch
 
 from . import _native as N
-from ._args import _flag, _index, _number
+from ._args import MAX_LENGTH, _flag, _index, _number
 from .equaliser import Equaliser
-from .frontend import MAX_LENGTH, FrontEnd, _host
+from .frontend import FrontEnd
+from .stage import Stage, _frames, _HeldFn, _host, _unframes, integers, no_cpu, pack, stage_for
 
 ORDERS = (1, 2, 4, 8)
 LAYOUTS = ("interleaved", "planar")          # iq_carrier_t.planar = 0, 1
@@ -115,13 +116,13 @@ def _order(order):
     return order
 
 
-def _layout(layout):
-    if layout not in LAYOUTS:
-        raise ValueError(f"layout must be one of {LAYOUTS}, got {layout!r}")
-    return LAYOUTS.index(layout)
+def _phases(arr):
+    if arr.size and (arr.min() < -2 ** 31 or arr.max() >= 2 ** 32):
+        raise ValueError("fth holds 32-bit phases (units of 2^-32 turn): an entry is out of range")
+    return (arr.astype(np.int64) & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
 
 
-class Carrier:
+class Carrier(Stage):
     """Frames of `length` samples -> the same frames with the carrier taken out.  order: M, the power that removes the
     modulation (2: BPSK, 4: QPSK and square QAM, 8: 8PSK; 1: a plain tone).  n_dft: the periodogram's size N >= length, an int
     (1024 * j, split by dft_factors) or a pair (n1, n2); None: default_n_dft(length).  f_max: the largest |frequency offset|
@@ -130,9 +131,11 @@ class Carrier:
     (B, length, 2), what the generators and the receiver write.  tables=: (t1, t2, tw) of one's own (dft_tables' shapes).
     Arguments are checked here, before any device work."""
 
+    LAYOUTS, reference = LAYOUTS, "carrier_reference"
+
     def __init__(self, length, order: int = 4, n_dft=None, f_max=None, refine: bool = True, layout: str = "planar", tables=None,
                  device="cuda"):
-        self.length = _index(length, "length", 1, MAX_LENGTH)
+        super().__init__(length, layout)
         self.order = _order(order)
         if n_dft is None:
             n_dft = default_n_dft(self.length)
@@ -155,56 +158,17 @@ class Carrier:
                 raise ValueError(f"f_max must be >= 0, got {f_max!r}")
             self.k_max = min(int(math.floor(self.f_max * self.order * self.n_dft)), self.n_dft // 2)
         self.refine = _flag(refine, "refine")
-        self.layout = layout
-        self.planar = _layout(layout)
         self.t1, self.t2, self.tw = _tables(tables, self.n1, self.n2)
         self.device = torch.device(device)
-        self._uploaded = {}
-
-    def frame_shape(self, B):
-        return (B, 2, self.length) if self.planar else (B, self.length, 2)
 
     def tables_on(self, device):
         """(t1, t2, tw) as fp32 tensors on `device`, uploaded once per device."""
-        t = self._uploaded.get(device)
-        if t is None:
-            device = torch.device(device)
-            if device.type == "cuda" and device.index is None:
-                device = torch.device("cuda", torch.cuda.current_device())
-            t = self._uploaded.get(device)
-            if t is None:
-                t = self._uploaded[device] = tuple(torch.from_numpy(a).to(device) for a in (self.t1, self.t2, self.tw))
-        return t
+        return self.table_on(device, ("t1", "t2", "tw"))
 
     def struct(self, tables=(None, None, None), fth=None, mode=1) -> N.Carrier:
         """The iq_carrier_t of one call (`tables`, `fth`: device addresses)."""
         return N.Carrier(order=self.order, n1=self.n1, n2=self.n2, k_max=self.k_max, refine=int(self.refine), planar=self.planar,
                          mode=mode, t1=tables[0], t2=tables[1], tw=tables[2], fth=fth)
-
-    def _check(self, x, fth, what="x"):
-        shape = self.frame_shape("B")
-        if not isinstance(x, torch.Tensor) or x.dim() != 3 or tuple(x.shape[1:]) != shape[1:]:
-            raise ValueError(f"{what} must be a {shape} tensor (layout {self.layout!r}), got "
-                             f"{tuple(x.shape) if hasattr(x, 'shape') else x!r}")
-        if fth is not None:
-            if not isinstance(fth, torch.Tensor):
-                try:
-                    arr = np.asarray(fth)
-                    if arr.dtype.kind not in "iu":
-                        raise TypeError
-                except (TypeError, ValueError):
-                    raise TypeError(f"fth must be a tensor or an array of integers, got {fth!r}") from None
-                if arr.size and (arr.min() < -2 ** 31 or arr.max() >= 2 ** 32):
-                    raise ValueError("fth holds 32-bit phases (units of 2^-32 turn): an entry is out of range")
-                fth = torch.from_numpy((arr.astype(np.int64) & 0xFFFFFFFF).astype(np.uint32).view(np.int32))
-            elif fth.dtype.is_floating_point or fth.dtype == torch.bool:
-                raise TypeError(f"fth must hold integers, got dtype {fth.dtype}")
-            if tuple(fth.shape) != (x.shape[0], 2):
-                raise ValueError(f"fth must have shape ({x.shape[0]}, 2) = (F, TH) per frame, got {tuple(fth.shape)}")
-        if not x.is_cuda:
-            raise N.IqError("Carrier runs on the MI355X only: x is a CPU tensor and there is no CPU fallback "
-                            "(carrier_reference is the host definition used by the tests)")
-        return None if fth is None else fth.to(device=x.device, dtype=torch.int32).contiguous()
 
     def __call__(self, x, fth=None, return_est=False, return_fth=False, return_power=False):
         """x: device frames in this carrier's layout, fp32 -> out of the same shape on the current stream, no host
@@ -216,58 +180,39 @@ class Carrier:
         return_power = _flag(return_power, "return_power")
         if return_power and fth is not None:
             raise ValueError("return_power needs the estimate: it is not computed with fth=")
-        fth = self._check(x, fth)
-        out, est, fth_out, power = _CarrierFn.apply(x, self, fth, return_est, return_power)
-        res = (out,)
-        if return_est:
-            res += (est,)
-        if return_fth:
-            res += (fth_out,)
-        if return_power:
-            res += (power,)
-        return res[0] if len(res) == 1 else res
+        self._check_shape(x)
+        if fth is not None:
+            fth = integers(fth, "fth", (x.shape[0], 2), x.device, " = (F, TH) per frame", _phases)
+        if not x.is_cuda:
+            raise no_cpu(self)
+        out, fth_out, est, power = _HeldFn.apply(x, self, fth, return_est, return_power)
+        return pack(out, est, fth_out if return_fth else None, power)
 
-    def __repr__(self):
-        return (f"Carrier(length={self.length}, order={self.order}, n_dft=({self.n1}, {self.n2}), f_max={self.f_max}, "
-                f"refine={self.refine}, layout={self.layout!r})")
-
-
-class _CarrierFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, cr, fth, want_est, want_power):
-        x = x.contiguous().float()
+    def _forward(self, x, fth, want_est, want_power):
         B, d = x.shape[0], x.device
         out = torch.empty_like(x)
         est = torch.empty(B, 4, dtype=torch.float32, device=d) if want_est else None
         fth_out = torch.empty(B, 2, dtype=torch.int32, device=d)         # the backward's (F, TH), held fixed
-        power = torch.empty(B, cr.n_dft, dtype=torch.float32, device=d) if want_power else None
+        power = torch.empty(B, self.n_dft, dtype=torch.float32, device=d) if want_power else None
         if B > 0:
-            tables = (None, None, None) if fth is not None else tuple(t.data_ptr() for t in cr.tables_on(d))
-            par = cr.struct(tables, N.ptr(fth), mode=0 if fth is not None else 1)
+            if fth is None:
+                t1, t2, tw = self.table_on(d, ("t1", "t2", "tw"))
+                par = self.struct((t1.data_ptr(), t2.data_ptr(), tw.data_ptr()))
+            else:
+                par = self.struct(fth=fth.data_ptr(), mode=0)
             N.check(N.lib().iq_frames_carrier(x.data_ptr(), out.data_ptr(), N.ptr(est), fth_out.data_ptr(), N.ptr(power), B,
-                                              cr.length, C.byref(par), torch.cuda.current_stream(d).cuda_stream),
+                                              self.length, C.byref(par), torch.cuda.current_stream(d).cuda_stream),
                     "iq_frames_carrier")
-        ctx.cr = cr
-        ctx.save_for_backward(fth_out)
-        ctx.mark_non_differentiable(fth_out)
-        if est is not None:
-            ctx.mark_non_differentiable(est)
-        if power is not None:
-            ctx.mark_non_differentiable(power)
-        return out, est, fth_out, power
+        return out, fth_out, (est, power)
 
-    @staticmethod
-    def backward(ctx, dout, _dest, _dfth, _dpower):
-        (fth,) = ctx.saved_tensors
-        cr = ctx.cr
-        dout = dout.contiguous().float()
-        dx = torch.empty_like(dout)
-        B = dout.shape[0]
-        if B > 0:
-            par = cr.struct(fth=fth.data_ptr(), mode=0)
-            N.check(N.lib().iq_frames_carrier_bwd(dout.data_ptr(), dx.data_ptr(), B, cr.length, C.byref(par),
-                                                  torch.cuda.current_stream(dout.device).cuda_stream), "iq_frames_carrier_bwd")
-        return dx, None, None, None, None
+    def _backward(self, dout, dx, fth, B):
+        par = self.struct(fth=fth.data_ptr(), mode=0)
+        N.check(N.lib().iq_frames_carrier_bwd(dout.data_ptr(), dx.data_ptr(), B, self.length, C.byref(par),
+                                              torch.cuda.current_stream(dout.device).cuda_stream), "iq_frames_carrier_bwd")
+
+    def __repr__(self):
+        return (f"Carrier(length={self.length}, order={self.order}, n_dft=({self.n1}, {self.n2}), f_max={self.f_max}, "
+                f"refine={self.refine}, layout={self.layout!r})")
 
 
 class Synchronised(FrontEnd):
@@ -282,19 +227,9 @@ class Synchronised(FrontEnd):
     def __init__(self, front, carrier, equaliser=None):
         if not isinstance(front, FrontEnd):
             raise TypeError(f"front must be a FrontEnd (Spectrogram, CyclicSpectrum, Constellation), got {type(front).__name__}")
-        if not isinstance(carrier, Carrier):
-            raise TypeError(f"carrier must be a Carrier, got {type(carrier).__name__}")
-        if not carrier.planar:
-            raise ValueError(f"the front ends read planar (B, 2, length) frames: the carrier's layout is {carrier.layout!r}")
-        if carrier.length != front.length:
-            raise ValueError(f"the carrier was built for frames of {carrier.length} samples, the front end for {front.length}")
-        if equaliser is not None:
-            if not isinstance(equaliser, Equaliser):
-                raise TypeError(f"equaliser must be an Equaliser or None, got {type(equaliser).__name__}")
-            if not equaliser.planar:
-                raise ValueError(f"the front ends read planar (B, 2, length) frames: the equaliser's layout is {equaliser.layout!r}")
-            if equaliser.length != front.length:
-                raise ValueError(f"the equaliser was built for frames of {equaliser.length} samples, the front end for {front.length}")
+        for stage, cls, what in ((carrier, Carrier, "carrier"), (equaliser, Equaliser, "equaliser")):
+            stage_for(stage, cls, what, True, front.length, "the front ends read planar (B, 2, length) frames",
+                      f"samples, the front end for {front.length}", optional=cls is Equaliser)
         super().__init__(front.length)
         self.front, self.carrier, self.equaliser = front, carrier, equaliser
         self.height, self.width, self.channels = front.height, front.width, front.channels
@@ -335,17 +270,6 @@ def _phasor(p):
     """e(p) of include/iqvit.h for integer phases p (int64, already wrapped): cos + j sin of pi * (float)(int32)p * 2^-31."""
     xf = np.asarray(p, dtype=np.int64).astype(np.float32).astype(np.float64) * 2.0 ** -31
     return np.cos(np.pi * xf) + 1j * np.sin(np.pi * xf)
-
-
-def _frames(x, planar):
-    x = _host(x).astype(np.float64)
-    if x.ndim != 3 or x.shape[1 if planar else 2] != 2:
-        raise ValueError(f"frames must be {'(B, 2, len)' if planar else '(B, len, 2)'}, got {x.shape}")
-    return (x[:, 0, :] + 1j * x[:, 1, :]) if planar else (x[:, :, 0] + 1j * x[:, :, 1])
-
-
-def _unframes(z, planar):
-    return np.stack([z.real, z.imag], axis=1 if planar else 2)
 
 
 def _fth(fth, B):

@@ -33,19 +33,13 @@ import torch
 
 from . import _native as N
 from ._args import _flag, _index, _number
-from .frontend import MAX_LENGTH, _host
+from .stage import Stage, _first_largest, _frames, _HeldFn, _host, _unframes, no_cpu, pack, reals
 
 LAYOUTS = ("frames", "planar")               # iq_equaliser_t.planar = 0: (B, length, 2), 1: (B, 2, length)
 MAX_TAPS, MAX_ITERS = 32, 4096               # the limits of iq_frames_equalise
 # The defaults: chosen on the host definition over mu in {0.005 .. 1.0} x iters in {16 .. 256} on the closed-loop frames of
 # tests/equaliser_ref.py ("Blind equaliser", has the sweep)
 DEFAULT_TAPS, DEFAULT_ITERS, DEFAULT_MU = 11, 64, 0.2
-
-
-def _layout(layout):
-    if layout not in LAYOUTS:
-        raise ValueError(f"layout must be one of {LAYOUTS}, got {layout!r}")
-    return LAYOUTS.index(layout)
 
 
 def _step(mu):
@@ -55,7 +49,7 @@ def _step(mu):
     return mu
 
 
-class Equaliser:
+class Equaliser(Stage):
     """Frames of `length` symbols -> the same frames through a blind `taps`-tap equaliser.  iters: the steps of the descent;
     mu: its step size (the gradient is the frame's mean, so mu does not depend on the length); modulus: R = E|a|^4 / E|a|^2 of
     the constellation at unit power (1 for PSK, 1.32 for 16QAM).  The input is expected at unit mean power (Receiver's
@@ -63,57 +57,20 @@ class Equaliser:
     what the carrier recovery in front of an image front end reads.  A call runs on the device its x lies on.  Arguments are
     checked here, before any device work."""
 
+    LAYOUTS, reference = LAYOUTS, "equaliser_reference"
+
     def __init__(self, length, taps: int = DEFAULT_TAPS, iters: int = DEFAULT_ITERS, mu: float = DEFAULT_MU, modulus: float = 1.0,
                  layout: str = "frames"):
-        self.length = _index(length, "length", 1, MAX_LENGTH)
+        super().__init__(length, layout)
         self.taps = _index(taps, "taps", 1, MAX_TAPS)
         self.iters = _index(iters, "iters", 0, MAX_ITERS)
         self.mu = _step(mu)
         self.modulus = _number(modulus, "modulus")
-        self.layout = layout
-        self.planar = _layout(layout)
-
-    def frame_shape(self, B):
-        return (B, 2, self.length) if self.planar else (B, self.length, 2)
 
     def struct(self, w=None, w0=None, mode=1) -> N.Equaliser:
         """The iq_equaliser_t of one call (`w`, `w0`: device addresses)."""
         return N.Equaliser(taps=self.taps, iters=self.iters, planar=self.planar, mode=mode, mu=self.mu, modulus=self.modulus,
                            w=w, w0=w0)
-
-    def _weights(self, w, what, B):
-        if w is None:
-            return None
-        if not isinstance(w, torch.Tensor):
-            try:
-                arr = np.asarray(w)
-                if arr.dtype.kind == "c":
-                    arr = np.stack([arr.real, arr.imag], axis=-1)
-                if arr.dtype.kind not in "fiu":
-                    raise TypeError
-            except (TypeError, ValueError):
-                raise TypeError(f"{what} must be a tensor or an array of numbers, got {w!r}") from None
-            w = torch.from_numpy(np.ascontiguousarray(arr, dtype=np.float32))
-        elif w.dtype.is_complex:
-            w = torch.view_as_real(w)
-        elif not w.dtype.is_floating_point:
-            raise TypeError(f"{what} must hold real or complex numbers, got dtype {w.dtype}")
-        if tuple(w.shape) != (B, self.taps, 2):
-            raise ValueError(f"{what} must have shape ({B}, {self.taps}, 2) = (re, im) per frame and tap, got {tuple(w.shape)}")
-        return w
-
-    def _check(self, x, w, w0, what="x"):
-        shape = self.frame_shape("B")
-        if not isinstance(x, torch.Tensor) or x.dim() != 3 or tuple(x.shape[1:]) != shape[1:]:
-            raise ValueError(f"{what} must be a {shape} tensor (layout {self.layout!r}), got "
-                             f"{tuple(x.shape) if hasattr(x, 'shape') else x!r}")
-        if w is not None and w0 is not None:
-            raise ValueError("w= gives the weights and w0= the start of the descent: pass one of them")
-        w, w0 = self._weights(w, "w", x.shape[0]), self._weights(w0, "w0", x.shape[0])
-        if not x.is_cuda:
-            raise N.IqError("Equaliser runs on the MI355X only: x is a CPU tensor and there is no CPU fallback "
-                            "(equaliser_reference is the host definition used by the tests)")
-        return tuple(None if t is None else t.to(device=x.device, dtype=torch.float32).contiguous() for t in (w, w0))
 
     def __call__(self, x, w=None, w0=None, return_w=False, return_est=False):
         """x: device frames in this equaliser's layout, fp32 -> out of the same shape on the current stream, no host
@@ -122,65 +79,39 @@ class Equaliser:
         taps // 2).  Then, if asked for, w (B, taps, 2) fp32 and est (B, 4) fp32 = {J before (NaN with w=), J after, sum |w|^2,
         index of the largest |w|}."""
         return_w, return_est = _flag(return_w, "return_w"), _flag(return_est, "return_est")
-        w, w0 = self._check(x, w, w0)
-        out, w_out, est = _EqualiseFn.apply(x, self, w, w0, return_est)
-        res = (out,)
-        if return_w:
-            res += (w_out,)
-        if return_est:
-            res += (est,)
-        return res[0] if len(res) == 1 else res
+        self._check_shape(x)
+        if w is not None and w0 is not None:
+            raise ValueError("w= gives the weights and w0= the start of the descent: pass one of them")
+        shape, note = (x.shape[0], self.taps, 2), " = (re, im) per frame and tap"
+        w = None if w is None else reals(w, "w", shape, x.device, note, pairs=True)
+        w0 = None if w0 is None else reals(w0, "w0", shape, x.device, note, pairs=True)
+        if not x.is_cuda:
+            raise no_cpu(self)
+        out, w_out, est = _HeldFn.apply(x, self, w, w0, return_est)
+        return pack(out, w_out if return_w else None, est)
+
+    def _forward(self, x, w, w0, want_est):
+        B, d = x.shape[0], x.device
+        out = torch.empty_like(x)
+        w_out = torch.empty(B, self.taps, 2, dtype=torch.float32, device=d)    # the backward's weights, held fixed
+        est = torch.empty(B, 4, dtype=torch.float32, device=d) if want_est else None
+        if B > 0:
+            par = self.struct(N.ptr(w), N.ptr(w0), mode=0 if w is not None else 1)
+            N.check(N.lib().iq_frames_equalise(x.data_ptr(), out.data_ptr(), w_out.data_ptr(), N.ptr(est), B, self.length,
+                                               C.byref(par), torch.cuda.current_stream(d).cuda_stream), "iq_frames_equalise")
+        return out, w_out, (est,)
+
+    def _backward(self, dout, dx, w, B):
+        par = self.struct(w=w.data_ptr(), mode=0)
+        N.check(N.lib().iq_frames_equalise_bwd(dout.data_ptr(), dx.data_ptr(), B, self.length, C.byref(par),
+                                               torch.cuda.current_stream(dout.device).cuda_stream), "iq_frames_equalise_bwd")
 
     def __repr__(self):
         return (f"Equaliser(length={self.length}, taps={self.taps}, iters={self.iters}, mu={self.mu}, modulus={self.modulus}, "
                 f"layout={self.layout!r})")
 
 
-class _EqualiseFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, eq, w, w0, want_est):
-        x = x.contiguous().float()
-        B, d = x.shape[0], x.device
-        out = torch.empty_like(x)
-        w_out = torch.empty(B, eq.taps, 2, dtype=torch.float32, device=d)      # the backward's weights, held fixed
-        est = torch.empty(B, 4, dtype=torch.float32, device=d) if want_est else None
-        if B > 0:
-            par = eq.struct(N.ptr(w), N.ptr(w0), mode=0 if w is not None else 1)
-            N.check(N.lib().iq_frames_equalise(x.data_ptr(), out.data_ptr(), w_out.data_ptr(), N.ptr(est), B, eq.length,
-                                               C.byref(par), torch.cuda.current_stream(d).cuda_stream), "iq_frames_equalise")
-        ctx.eq = eq
-        ctx.save_for_backward(w_out)
-        ctx.mark_non_differentiable(w_out)
-        if est is not None:
-            ctx.mark_non_differentiable(est)
-        return out, w_out, est
-
-    @staticmethod
-    def backward(ctx, dout, _dw, _dest):
-        (w,) = ctx.saved_tensors
-        eq = ctx.eq
-        dout = dout.contiguous().float()
-        dx = torch.empty_like(dout)
-        B = dout.shape[0]
-        if B > 0:
-            par = eq.struct(w=w.data_ptr(), mode=0)
-            N.check(N.lib().iq_frames_equalise_bwd(dout.data_ptr(), dx.data_ptr(), B, eq.length, C.byref(par),
-                                                   torch.cuda.current_stream(dout.device).cuda_stream), "iq_frames_equalise_bwd")
-        return dx, None, None, None, None
-
-
 # ---- the host definition
-
-def _frames(x, planar):
-    x = _host(x).astype(np.float64)
-    if x.ndim != 3 or x.shape[1 if planar else 2] != 2:
-        raise ValueError(f"frames must be {'(B, 2, len)' if planar else '(B, len, 2)'}, got {x.shape}")
-    return (x[:, 0, :] + 1j * x[:, 1, :]) if planar else (x[:, :, 0] + 1j * x[:, :, 1])
-
-
-def _unframes(z, planar):
-    return np.stack([z.real, z.imag], axis=1 if planar else 2)
-
 
 def _complex_weights(w, B, L, what):
     w = _host(w)
@@ -244,12 +175,7 @@ def equaliser_reference(x, taps, iters, mu, modulus=1.0, planar=False, w=None, w
     est[:, 1] = J
     p = wc.real ** 2 + wc.imag ** 2
     est[:, 2] = p.sum(axis=1)
-    at, best = np.zeros(B, np.int64), p[:, 0].copy()
-    for l in range(1, L):                                     # the first largest; a NaN is never larger (nor ever beaten)
-        with np.errstate(invalid="ignore"):
-            up = p[:, l] > best
-        at[up], best[up] = l, p[up, l]
-    est[:, 3] = at
+    est[:, 3] = _first_largest(p, 1)[0]
     return _unframes(y, planar), np.stack([wc.real, wc.imag], axis=2), est
 
 

@@ -4,23 +4,18 @@ ViT reads, by one HIP launch per direction.
 spectrogram.Spectrogram, cyclic.CyclicSpectrum and constellation.Constellation derive from `FrontEnd`.  A front end writes what
 is its own: its arguments and tables, `struct()` (the parameter struct of a call), `_forward` / `_backward` (each exactly one C
 call, with its tables) and its host fp64 definition.  Everything else is here, once, and no method here knows which subclass
-calls it: the refusals of `_check`, the call through one autograd function, the launch routine, `fit`, the per-device table
-cache and the checks of the scaling arguments.  `front_end` is the `spectrogram=` argument of the input paths (data.py,
-synth.py, impairments.py), which read a front end through `length`, `height` and `width` only.
+calls it: the refusals of `_check`, the call through one autograd function, the launch routine, `fit` and the checks of the
+scaling arguments.  The per-device table cache and the CPU refusal are stage.py's: the symbol-rate stages share them.
+`front_end` is the `spectrogram=` argument of the input paths (data.py, synth.py, impairments.py), which read a front end
+through `length`, `height` and `width` only.
 """
 from __future__ import annotations
 
 import numpy as np
 import torch
 
-from . import _native as N
-from ._args import _index, _number
-
-MAX_LENGTH = 8192            # one workgroup keeps one frame in LDS: len * 8 bytes <= 64 KB
-
-
-def _host(a):
-    return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+from ._args import MAX_LENGTH, _index, _number
+from .stage import DeviceTables, _host, no_cpu  # noqa: F401  (_host: the front ends' host definitions import it from here)
 
 
 def _mode(mode, modes):
@@ -37,9 +32,9 @@ def _image_geometry(model):
     return geom
 
 
-class FrontEnd:
+class FrontEnd(DeviceTables):
     """The protocol.  A subclass sets `height` and `width` (and `channels`, unless 1), names its host definition in `reference`,
-    keeps its tables as numpy attributes (`table_on` uploads them by name) and supplies
+    keeps its tables as numpy attributes (stage.DeviceTables' `table_on` uploads them by name) and supplies
       struct()                                 the parameter struct of a call, from the object as it is now
       _forward(x, out, B, par, stream)         the one C call x -> out            (B > 0, x contiguous fp32)
       _backward(x, dout, dx, B, par, stream)   the one C call (x, dout) -> dx     (B > 0, par the struct of the forward call)"""
@@ -55,18 +50,6 @@ class FrontEnd:
     def image_shape(self, B):
         return (B, self.channels, self.height, self.width)
 
-    def table_on(self, device, name="table"):
-        """The numpy table `self.<name>` as an fp32 tensor on `device`, uploaded once per device."""
-        t = self._uploaded.get((name, device))               # a call's x.device: found as it is
-        if t is None:
-            device = torch.device(device)
-            if device.type == "cuda" and device.index is None:
-                device = torch.device("cuda", torch.cuda.current_device())
-            t = self._uploaded.get((name, device))
-            if t is None:
-                t = self._uploaded[name, device] = torch.from_numpy(getattr(self, name)).to(device)
-        return t
-
     def _set_scaling(self, floor, scale, shift):
         self.floor = _number(floor, "floor")                 # of a log or a division: positive after rounding to fp32
         if self.floor <= 0 or float(np.float32(self.floor)) <= 0:
@@ -78,8 +61,7 @@ class FrontEnd:
             raise ValueError(f"{what} must be a (B, 2, {self.length}) tensor, got "
                              f"{tuple(x.shape) if hasattr(x, 'shape') else x!r}")
         if not x.is_cuda:
-            raise N.IqError(f"{type(self).__name__} runs on the MI355X only: x is a CPU tensor and there is no CPU fallback "
-                            f"({self.reference} is the host definition used by the tests)")
+            raise no_cpu(self)
         if not self.differentiable and x.requires_grad and torch.is_grad_enabled():
             raise RuntimeError(f"this {type(self).__name__} is not differentiable: build it with differentiable=True for "
                                "gradients down to the signal, or pass x.detach()")

@@ -27,7 +27,6 @@ classifiers, and the backward.
 from __future__ import annotations
 
 import ctypes as C
-import math
 
 import numpy as np
 import torch
@@ -35,7 +34,7 @@ import torch
 from . import _native as N
 from . import data as D
 from ._args import _flag, _index
-from .frontend import MAX_LENGTH, _host
+from .stage import Stage, _first_largest, _frames, _host, no_cpu, pack, reals
 from .synth import SHAPED, _points
 
 LAYOUTS = ("frames", "planar")               # iq_likelihood_t.planar = 0: (B, length, 2), 1: (B, 2, length)
@@ -82,7 +81,7 @@ def rotation_table(angles):
     return np.stack([np.cos(ang), np.sin(ang)], axis=1).astype(np.float32)
 
 
-class LikelihoodClassifier:
+class LikelihoodClassifier(Stage):
     """Frames of `length` symbols at one sample per symbol -> the log-likelihood of each of the classes.  classes: names
     data.constellation knows (default: its 17, in data.CLASSES' order), (name, points) pairs or {name: points} for constellations
     of one's own, scaled to unit mean power in fp64 and rounded to the fp32 table as FrameSynth does.  rotations: a count R
@@ -90,8 +89,10 @@ class LikelihoodClassifier:
     'frames' (B, length, 2) or 'planar' (B, 2, length).  A call runs on the device its x lies on.  Arguments are checked here,
     before any device work."""
 
+    LAYOUTS, reference = LAYOUTS, "likelihood_reference"
+
     def __init__(self, length, classes=None, rotations=64, mode: str = "max", layout: str = "frames"):
-        self.length = _index(length, "length", 1, MAX_LENGTH)
+        super().__init__(length, layout)
         if classes is None:
             classes = TABLE_CLASSES
         if isinstance(classes, str):
@@ -128,11 +129,8 @@ class LikelihoodClassifier:
         self.rot = rotation_table(self.angles)                                                # (R, 2): the kernel's table
         if mode not in MODES:
             raise ValueError(f"mode must be one of {MODES}, got {mode!r}")
-        if layout not in LAYOUTS:
-            raise ValueError(f"layout must be one of {LAYOUTS}, got {layout!r}")
-        self.mode, self.layout, self.planar = mode, layout, LAYOUTS.index(layout)
+        self.mode = mode
         self._classes_c = (N.SynthClass * len(self.descriptors))(*[N.SynthClass(*d) for d in self.descriptors])
-        self._uploaded = {}
 
     @property
     def n_classes(self):
@@ -142,60 +140,27 @@ class LikelihoodClassifier:
     def n_rotations(self):
         return len(self.angles)
 
-    def frame_shape(self, B):
-        return (B, 2, self.length) if self.planar else (B, self.length, 2)
-
     def tables_on(self, device):
         """(points, rot) as fp32 tensors on `device`, uploaded once per device."""
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        t = self._uploaded.get(device)
-        if t is None:
-            t = self._uploaded[device] = (torch.from_numpy(self.points).to(device), torch.from_numpy(self.rot).to(device))
-        return t
+        return self.table_on(device, ("points", "rot"))
 
     def struct(self, points=None, rot=None, gain=None) -> N.Likelihood:
         """The iq_likelihood_t of one call (`points`, `rot`, `gain`: device addresses)."""
         return N.Likelihood(points=points, classes=self._classes_c, n_classes=self.n_classes, rot=rot, n_rot=self.n_rotations,
                             planar=self.planar, mode=MODES.index(self.mode), gain=gain)
 
-    def _per_frame(self, v, what, B):
-        """A number, an array or a tensor of B values -> fp32 (B,), still wherever it was."""
-        if isinstance(v, torch.Tensor):
-            if v.dtype.is_complex or v.dtype == torch.bool:
-                raise TypeError(f"{what} must hold real numbers, got dtype {v.dtype}")
-            t = v.to(torch.float32)
-        else:
-            try:
-                arr = np.asarray(v)
-                if arr.dtype.kind not in "fiu":
-                    raise TypeError
-            except (TypeError, ValueError):
-                raise TypeError(f"{what} must be a number, an array or a tensor of real numbers, got {v!r}") from None
-            t = torch.from_numpy(np.array(arr, dtype=np.float32))
-        if t.dim() == 0:
-            t = t.expand(B)
-        if tuple(t.shape) != (B,):
-            raise ValueError(f"{what} must be a number or have shape ({B},), one value per frame, got {tuple(t.shape)}")
-        return t
-
     def _check(self, x, sigma2, snr_db, gain):
-        shape = self.frame_shape("B")
-        if not isinstance(x, torch.Tensor) or x.dim() != 3 or tuple(x.shape[1:]) != shape[1:]:
-            raise ValueError(f"x must be a {shape} tensor (layout {self.layout!r}), got "
-                             f"{tuple(x.shape) if hasattr(x, 'shape') else x!r}")
+        self._check_shape(x)
         if (sigma2 is None) == (snr_db is None):
             raise ValueError("pass the noise as sigma2= (the variance per frame) or as snr_db= (generator convention): one of them")
-        B = x.shape[0]
+        shape, note = (x.shape[0],), ", one value per frame"
         if sigma2 is None:
-            sigma2 = noise_for(self._per_frame(snr_db, "snr_db", B))[1]
-        sigma2 = self._per_frame(sigma2, "sigma2", B)
-        gain = None if gain is None else self._per_frame(gain, "gain", B)
+            sigma2 = noise_for(reals(snr_db, "snr_db", shape, None, note))[1]
+        sigma2 = reals(sigma2, "sigma2", shape, x.device, note)
+        gain = None if gain is None else reals(gain, "gain", shape, x.device, note)
         if not x.is_cuda:
-            raise N.IqError("LikelihoodClassifier runs on the MI355X only: x is a CPU tensor and there is no CPU fallback "
-                            "(likelihood_reference is the host definition used by the tests)")
-        return tuple(None if t is None else t.to(device=x.device, dtype=torch.float32).contiguous() for t in (sigma2, gain))
+            raise no_cpu(self)
+        return sigma2, gain
 
     def _run(self, x, sigma2, snr_db, gain, want_rot, want_best, want_pred):
         sigma2, gain = self._check(x, sigma2, snr_db, gain)
@@ -206,7 +171,7 @@ class LikelihoodClassifier:
         best = torch.empty(B, Cn, dtype=torch.int32, device=d) if want_best else None
         pred = torch.empty(B, dtype=torch.int32, device=d) if want_pred else None
         if B > 0:
-            points, rot = self.tables_on(d)
+            points, rot = self.table_on(d, ("points", "rot"))
             par = self.struct(points.data_ptr(), rot.data_ptr(), N.ptr(gain))
             N.check(N.lib().iq_frames_likelihood(x.data_ptr(), sigma2.data_ptr(), loglik.data_ptr(), N.ptr(rot_ll), N.ptr(best),
                                                  N.ptr(pred), B, self.length, C.byref(par),
@@ -221,8 +186,7 @@ class LikelihoodClassifier:
         not a positive finite number gets NaN (best_rot -1)."""
         return_rot, return_best = _flag(return_rot, "return_rot"), _flag(return_best, "return_best")
         loglik, rot_ll, best, _ = self._run(x, sigma2, snr_db, gain, return_rot, return_best, False)
-        res = (loglik,) + tuple(t for t in (rot_ll, best) if t is not None)
-        return res[0] if len(res) == 1 else res
+        return pack(loglik, rot_ll, best)
 
     def predict(self, x, sigma2=None, snr_db=None, gain=None):
         """-> (B,) int64: the first class with the largest log-likelihood; -1 for a frame whose sigma2 is refused."""
@@ -237,27 +201,13 @@ class LikelihoodClassifier:
 
 # ---- the host definition
 
-def _first_largest(v, axis):
-    """Index of the first largest along `axis`; a NaN is never larger nor ever beaten (the kernel's walk)."""
-    v = np.moveaxis(v, axis, 0)
-    at, best = np.zeros(v.shape[1:], np.int64), v[0].copy()
-    for i in range(1, len(v)):
-        with np.errstate(invalid="ignore"):
-            up = v[i] > best
-        at[up], best[up] = i, v[i][up]
-    return at, best
-
-
 def likelihood_reference(x, sigma2, gain, points, classes, angles, mode="max", planar=False):
     """The definition of include/iqvit.h in fp64 on the host.  x: (B, len, 2) or, planar, (B, 2, len); sigma2: (B,) or a number;
     gain: (B,), a number or None (1); points: (P, 2) or complex (P,); classes: (offset, count) or (kind, offset, count) per class;
     angles: (R,) in radians, or the (R, 2) table of (cos, sin) itself; mode: 'max' / 'mean' (or IQ_LIK_*).
     -> loglik (B, C), L (B, C, R) float64, best_rot (B, C), pred (B,) int64.  A frame whose sigma2 is not a positive finite
     number has NaN in loglik and L and -1 in best_rot and pred."""
-    x = _host(x).astype(np.float64)
-    if x.ndim != 3 or x.shape[1 if planar else 2] != 2:
-        raise ValueError(f"frames must be {'(B, 2, len)' if planar else '(B, len, 2)'}, got {x.shape}")
-    y = (x[:, 0, :] + 1j * x[:, 1, :]) if planar else (x[:, :, 0] + 1j * x[:, :, 1])
+    y = _frames(x, planar)
     B, n = y.shape
     s2 = np.broadcast_to(np.asarray(_host(sigma2), dtype=np.float64), (B,))
     a = np.ones(B) if gain is None else np.broadcast_to(np.asarray(_host(gain), dtype=np.float64), (B,))

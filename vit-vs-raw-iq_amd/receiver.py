@@ -25,8 +25,11 @@ import numpy as np
 import torch
 
 from . import _native as N
-from ._args import _flag, _index, _number
-from .synth import MAX_LENGTH, FrameSynth
+from ._args import MAX_LENGTH, _flag, _index, _number
+from .carrier import Carrier
+from .equaliser import Equaliser
+from .stage import DeviceTables, _host, integers, no_cpu, pack, stage_for
+from .synth import FrameSynth
 from .waveform import ShapedSynth, rrc_pulse
 
 MAX_SPS, MAX_SPAN, MAX_FRAC = 16, 32, 64      # the limits of iq_frames_receive
@@ -77,12 +80,14 @@ def _table(v, shape):
     return np.ascontiguousarray(t.astype(np.float32))
 
 
-class Receiver:
+class Receiver(DeviceTables):
     """raw (B, len, 2) frames at `sps` samples per symbol -> (B, len // sps, 2) symbols.  span: matched-filter length in
     symbols; alpha: roll-off of its root-raised cosine; n_frac: fractional sampling phases in the table.  timing:
     'oerder_meyr' (the phase of the symbol-rate line of |y|^2: sps >= 3), 'energy' (the sample phase of most energy) or 'given'
     (the caller's u, in units of 1 / n_frac sample).  normalise: unit mean power per frame.  table=: a table of one's own,
     (n_frac, sps * span + 1).  Arguments are checked here, before any device work."""
+
+    reference = "receiver_reference"
 
     def __init__(self, sps, span: int = 8, alpha: float = 0.35, n_frac: int = 32, timing: str = "oerder_meyr",
                  normalise: bool = True, table=None, device="cuda"):
@@ -94,7 +99,7 @@ class Receiver:
         shape = (self.n_frac, self.sps * self.span + 1)
         self.table = mf_table(self.alpha, self.sps, self.span, self.n_frac) if table is None else _table(table, shape)
         self.device = torch.device(device)
-        self._tables = {}
+        self._uploaded = {}
 
     @classmethod
     def for_synth(cls, shaped, **kw):
@@ -113,16 +118,6 @@ class Receiver:
         return N.Receiver(sps=self.sps, span=self.span, n_frac=self.n_frac, mode=self.mode if mode is None else mode,
                           normalise=int(self.normalise), table=table, u=u)
 
-    def table_on(self, device):
-        """The fp32 table on `device` (uploaded once per device)."""
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        t = self._tables.get(device)
-        if t is None:
-            t = self._tables[device] = torch.from_numpy(self.table).to(device)
-        return t
-
     def _check(self, raw, u):
         if not isinstance(raw, torch.Tensor) or raw.dim() != 3 or raw.shape[2] != 2:
             raise ValueError(f"raw must be a (B, len, 2) tensor, got {tuple(raw.shape) if hasattr(raw, 'shape') else raw!r}")
@@ -131,24 +126,14 @@ class Receiver:
         if u is not None:
             if self.mode != 0:
                 raise ValueError(f"u is for timing='given', this receiver estimates it (timing={self.timing!r})")
-            if not isinstance(u, torch.Tensor):
-                try:
-                    arr = np.asarray(u)
-                    if arr.dtype.kind not in "iu":
-                        raise TypeError
-                except (TypeError, ValueError):
-                    raise TypeError(f"u must be a tensor or an array of integers, got {u!r}") from None
+            def in_range(arr):                   # (called before u is bound anew: u is still the caller's)
                 if arr.size and (arr.min() < 0 or arr.max() >= self.sps * self.n_frac):
                     raise ValueError(f"u must be in [0, sps * n_frac) = [0, {self.sps * self.n_frac}), got {u!r}")
-                u = torch.from_numpy(arr.astype(np.int32))
-            elif u.dtype.is_floating_point or u.dtype == torch.bool:
-                raise TypeError(f"u must hold integers, got dtype {u.dtype}")
-            if tuple(u.shape) != (raw.shape[0],):
-                raise ValueError(f"u must have shape ({raw.shape[0]},), got {tuple(u.shape)}")
+                return arr.astype(np.int32)
+            u = integers(u, "u", (raw.shape[0],), raw.device, wrap=in_range)
         if not raw.is_cuda:
-            raise N.IqError("Receiver runs on the MI355X only: raw is a CPU tensor and there is no CPU fallback "
-                            "(receiver_reference is the host definition used by the tests)")
-        return None if u is None else u.to(device=raw.device, dtype=torch.int32).contiguous()
+            raise no_cpu(self, "raw")
+        return u
 
     def __call__(self, raw, u=None, return_est=False, return_energy=False):
         """raw: device (B, len, 2) fp32 -> sym (B, len // sps, 2) fp32 on the current stream, no host synchronisation;
@@ -159,12 +144,7 @@ class Receiver:
         return_est, return_energy = _flag(return_est, "return_est"), _flag(return_energy, "return_energy")
         u = self._check(raw, u)
         sym, est, energy = _ReceiveFn.apply(raw, self, u, return_est, return_energy)
-        out = (sym,)
-        if return_est:
-            out += (est,)
-        if return_energy:
-            out += (energy,)
-        return out[0] if len(out) == 1 else out
+        return pack(sym, est if return_est else None, energy)
 
     def __repr__(self):
         return (f"Receiver(sps={self.sps}, span={self.span}, alpha={self.alpha}, n_frac={self.n_frac}, timing={self.timing!r}, "
@@ -189,10 +169,7 @@ class _ReceiveFn(torch.autograd.Function):
                                               torch.cuda.current_stream(d).cuda_stream), "iq_frames_receive")
         ctx.rx, ctx.u, ctx.table, ctx.length = rx, u, table, length
         ctx.save_for_backward(sym, est)
-        if est is not None:
-            ctx.mark_non_differentiable(est)
-        if energy is not None:
-            ctx.mark_non_differentiable(energy)
+        ctx.mark_non_differentiable(*[t for t in (est, energy) if t is not None])
         return sym, est, energy
 
     @staticmethod
@@ -230,17 +207,9 @@ class ReceivedSynth(FrameSynth):
         self.class_names, self.descriptors, self.points = shaped.class_names, shaped.descriptors, shaped.points
         self.snrs_db, self.seed, self.balanced, self.device = shaped.snrs_db, shaped.seed, shaped.balanced, shaped.device
         self.length = receiver.n_out(shaped.length)
-        from .carrier import Carrier             # (carrier.py imports the front ends, which import synth.py as this file does)
-        from .equaliser import Equaliser
         for stage, cls, what in ((equaliser, Equaliser, "equaliser"), (carrier, Carrier, "carrier")):
-            if stage is None:
-                continue
-            if not isinstance(stage, cls):
-                raise TypeError(f"{what} must be {'an' if what[0] == 'e' else 'a'} {cls.__name__} or None, got {type(stage).__name__}")
-            if stage.planar:
-                raise ValueError(f"the receiver writes (B, length, 2) frames: the {what}'s layout is {stage.layout!r}")
-            if stage.length != self.length:
-                raise ValueError(f"the {what} was built for frames of {stage.length} symbols, the receiver gives {self.length}")
+            stage_for(stage, cls, what, False, self.length, "the receiver writes (B, length, 2) frames",
+                      f"symbols, the receiver gives {self.length}")
         self.equaliser, self.carrier = equaliser, carrier
 
     def _stages(self, sym):
@@ -265,10 +234,6 @@ class ReceivedSynth(FrameSynth):
     def __repr__(self):
         more = "".join(f", {k}={v!r}" for k, v in (("equaliser", self.equaliser), ("carrier", self.carrier)) if v is not None)
         return f"ReceivedSynth({self.shaped!r}, {self.receiver!r}{more})"
-
-
-def _host(a):
-    return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
 
 
 def _windows(raw, table, sps):

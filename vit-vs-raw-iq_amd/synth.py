@@ -32,13 +32,12 @@ import torch
 
 from . import _native as N
 from . import data as D
-from ._args import _flag, _index, _number
+from ._args import MAX_LENGTH, _flag, _index, _number
 from .frontend import front_end
 from .impairments import Impairments, _stats4, _take
 
 KIND_POINTS, KIND_GMSK, KIND_OQPSK = 0, 1, 2
 SHAPED = {"GMSK": KIND_GMSK, "OQPSK": KIND_OQPSK}
-MAX_LENGTH = 8192            # one workgroup keeps one frame in LDS: len * 8 bytes <= 64 KB
 MAX_CLASSES, MAX_SNRS = 128, 64      # IQ_SYNTH_MAX_CLASSES, IQ_SYNTH_MAX_SNRS
 
 
