@@ -800,6 +800,61 @@ int iq_frames_likelihood(const float* x, const float* sigma2 /*[n]*/, float* log
                          float* rot_ll /*NULL or [n, C, R]*/, int* best_rot /*NULL or [n, C]*/,
                          int* pred /*NULL or [n]*/, int n_frames, int len,
                          const iq_likelihood_t* par, iq_stream_t stream);
+/* Cumulant classifier (csrc/cumulants.hip): the feature-based baseline of modulation classification beside the likelihood test
+ * (higher-order cumulants in the style of Swami & Sadler).  For every frame the mean, the central moments and the cumulants up to
+ * order eight, ten features that no carrier rotation changes, and the weighted distance of the features to every class's
+ * centroid.  O(len) per frame; Gaussian noise leaves every cumulant above order two in expectation, so sigma2 may be left out.
+ * x: fp32 frames of len symbols at one sample per symbol, planar = 0: [n_frames, len, 2]; planar = 1: [n_frames, 2, len];
+ * y[n] = I[n] + j Q[n].  With z = y - m and M_pq = mean(z^(p-q) conj(z)^q), all arithmetic fp32, every operation rounded once,
+ * in this order (fmaf is the fused multiply-add; (a, b) is a complex number by its parts; nothing else is fused):
+ *   sums           the symbols of a lane ascending from +0; then the wave's butterfly (xor 32, 16, 8, 4, 2, 1); then, on the
+ *                  workgroup route, the four waves ((w0 + w1) + w2) + w3.  len <= 256 (the wave route): lane l of one wave has
+ *                  the symbols l, l + 64, ...; len > 256 (the workgroup route): thread t of 256 has t, t + 256, ...
+ *   m              = (sum Re y / (float)len, sum Im y / (float)len)  (IEEE division), the frame read once and kept in LDS
+ *   per symbol     z = (a, b) = (Re y - Re m, Im y - Im m);  sq(u) = (fmaf(u.re, u.re, -(u.im * u.im)), (u.re + u.re) * u.im);
+ *                  u v = (fmaf(u.re, v.re, -(u.im * v.im)), fmaf(u.re, v.im, u.im * v.re));  |u|^2 = fmaf(u.im, u.im, u.re * u.re);
+ *                  z2 = sq(z), z4 = sq(z2), z6 = z4 z2, z8 = sq(z4), r = |z|^2, r2 = r * r, and the 17 terms
+ *                  z2 | r | z4 | z2 * r | r2 | z6 | z4 * r | z2 * r2 | r2 * r | z8
+ *   moments        each sum / (float)len:  M20 | M21 | M40 | M41 | M42 | M60 | M61 | M62 | M63 | M80  (M21, M42, M63 real)
+ *   cumulants      of the pair (z, conj z), by the moment-to-cumulant partition formula; s u + v below is (fmaf(s, u.re, v.re),
+ *                  fmaf(s, u.im, v.im)), q = sq(M20), n = |M20|^2, conj(u) v = (fmaf(u.re, v.re, u.im * v.im), fmaf(u.re, v.im, -(u.im * v.re)))
+ *                  C20 = M20;  C21 = M21;  C40 = -3 q + M40;  C41 = -(3 * M21) M20 + M41;
+ *                  C42 = fmaf(-(M21 + M21), M21, M42 - n)
+ *                  C60 = 30 (q M20) + (-15 (M20 M40) + M60)
+ *                  C61 = (30 * M21) q + (-10 (M20 M41) + (-(5 * M21) M40 + M61))
+ *                  C62 = g M20 + ((-(8 * M21) M41 + (-(6 * M42) M20 + M62)) - conj(M20) M40),  g = fmaf(24 * M21, M21, 6 * n)
+ *                  C63 = fmaf(18 * n, M21, fmaf(-6, h, fmaf(12 * (M21 * M21), M21, fmaf(-(9 * M21), M42, M63)))),
+ *                        h = fmaf(Re M20, Re M41, Im M20 * Im M41)
+ *                  C80 = -630 sq(q) + (420 (q M40) + (-35 sq(M40) + (-28 (M20 M60) + M80)))
+ *   P              = C21 - sigma2[b] (sigma2 NULL: - 0): the signal's variance.  P2 = P * P, P3 = P2 * P, P4 = P3 * P
+ *   feat[b, 0..9]  |m|^2 / P | |C20| / P | |C40| / P2 | |C41| / P2 | C42 / P2 | |C60| / P3 | |C61| / P3 | |C62| / P3 | C63 / P3 |
+ *                  |C80| / P4,  |u| = sqrt(|u|^2) (IEEE square root and division)
+ *   score[b, c]    = bias[c] - acc (bias NULL: 0 - acc),  acc from +0, f ascending: d = feat[f] - mu[c, f];
+ *                  acc = fmaf(w[c, f] * d, d, acc)
+ *   pred[b]        the first c with the largest score[b, c] (c ascending; a NaN is never larger nor ever beaten)
+ * mom[b, 0..19] = Re m, Im m, then the moments in the order above (complex ones as re, im), then P.
+ * P is data, not an argument: a frame whose P is not a positive finite number (an all-zero frame, len = 1, a sigma2 at or above
+ * the frame's variance, a NaN sample) gets NaN in every feature and every score and -1 in pred; mom is written as computed; no
+ * other frame is touched.
+ * Outputs, each NULL or: feat fp32 [n_frames, 10]; mom fp32 [n_frames, 20]; score fp32 [n_frames, C]; pred int32 [n_frames].  One
+ * launch.  No atomics, no workspace, two runs agree bit for bit and a frame's outputs depend on neither n_frames nor its
+ * position.  LDS: the frame, len * 8 bytes (four frames on the wave route), and 304 bytes.  There is no backward.
+ * IQ_STATUS_ARG before any HIP call, outputs untouched: NULL x / par; all four outputs NULL; len < 1; planar outside {0,1};
+ * n_classes < 0; n_classes > 0 with NULL mu or w; score or pred with n_classes == 0; x not 8-byte (planar = 0) or 4-byte
+ * (planar = 1) aligned, any other pointer not 4-byte aligned.
+ * IQ_STATUS_UNSUPPORTED: C > 64, len * 8 bytes above 64 KB (the frame kernels' limit), n_frames * max(C, 20) above 2^31 - 1.
+ * n_frames <= 0: success, nothing is launched. */
+typedef struct iq_cumulants {
+  int planar;            /* 0: x [n, len, 2]; 1: [n, 2, len] */
+  const float* sigma2;   /* DEVICE fp32 [n] or NULL (= 0: blind) */
+  const float* mu;       /* DEVICE fp32 [C, 10]; NULL iff n_classes == 0 */
+  const float* w;        /* DEVICE fp32 [C, 10] */
+  const float* bias;     /* DEVICE fp32 [C] or NULL (= 0) */
+  int n_classes;         /* C in [0, 64]; 0: features only */
+} iq_cumulants_t;
+int iq_frames_cumulants(const float* x, float* feat /*NULL or [n,10]*/, float* mom /*NULL or [n,20]*/,
+                        float* score /*NULL or [n,C]*/, int* pred /*NULL or [n]*/,
+                        int n_frames, int len, const iq_cumulants_t* par, iq_stream_t stream);
 int iq_patchify(const float* src, void* patches, int kind, int B, int C, int H, int W, int p, int Kpad,
                 iq_stream_t stream);
 int iq_cls_rows(const float* cls, const float* pe, void* x0, int B, int S, int D, const iq_dropout_t* drop,

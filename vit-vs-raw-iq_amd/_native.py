@@ -82,6 +82,11 @@ class Likelihood(C.Structure):
                 ("n_rot", C.c_int), ("planar", C.c_int), ("mode", C.c_int), ("gain", C.c_void_p)]
 
 
+class Cumulants(C.Structure):
+    _fields_ = [("planar", C.c_int), ("sigma2", C.c_void_p), ("mu", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p),
+                ("n_classes", C.c_int)]
+
+
 class Cyclic(C.Structure):
     _fields_ = [("n_fft", C.c_int), ("hop", C.c_int), ("pad", C.c_int), ("columns", C.c_int), ("kind", C.c_int),
                 ("mode", C.c_int), ("inv_norm", C.c_float), ("floor", C.c_float), ("scale", C.c_float), ("shift", C.c_float)]
@@ -180,6 +185,7 @@ SIGNATURES = {
     "iq_frames_equalise": (_I, [_P, _P, _P, _P, _I, _I, C.POINTER(Equaliser), _P]),
     "iq_frames_equalise_bwd": (_I, [_P, _P, _I, _I, C.POINTER(Equaliser), _P]),
     "iq_frames_likelihood": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, C.POINTER(Likelihood), _P]),
+    "iq_frames_cumulants": (_I, [_P, _P, _P, _P, _P, _I, _I, C.POINTER(Cumulants), _P]),
     "iq_patchify": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "iq_cls_rows": (_I, [_P, _P, _P, _I, _I, _I, C.POINTER(Dropout), _P]),
     "iq_embed_bwd_gather": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, C.POINTER(Dropout), _I, _P]),

@@ -130,3 +130,26 @@ def evaluate_likelihood_with_confusion(clf, dataloader: Iterable, device: torch.
     if list(class_names) != list(clf.class_names):
         raise ValueError(f"class_names must be the classifier's classes {clf.class_names!r}, got {list(class_names)!r}")
     return _evaluate_with_confusion(lambda x, y, z: clf.predict(x, snr_db=z), dataloader, device, class_names, save_dir, prefix)
+
+
+@torch.no_grad()
+def evaluate_cumulants_with_confusion(clf, dataloader: Iterable, device: torch.device, class_names: List[str], save_dir: Path,
+                                      prefix: str = "test", known_noise: bool = False) -> Dict:
+    """The same evaluation and the same report file for a cumulants.CumulantClassifier: a fourth column for compare_models.py.
+    `dataloader` yields (frames, labels, snrs) with frames in the classifier's layout; labels index `class_names`, which must
+    be the classifier's classes.  known_noise: False decides blind; True hands the classifier snr_db = `snrs` (generator
+    convention: a unit-power signal plus noise), and a frame whose noise variance is then at or above its own variance is
+    decided blind.  A frame without any variance (pred -1 in both) is counted under class 0."""
+    device = torch.device(device)
+    if list(class_names) != list(clf.class_names):
+        raise ValueError(f"class_names must be the classifier's classes {clf.class_names!r}, got {list(class_names)!r}")
+    if not isinstance(known_noise, bool):
+        raise TypeError(f"known_noise must be True or False, got {known_noise!r}")
+
+    def predict(x, y, z):
+        p = clf.predict(x)
+        if known_noise:
+            k = clf.predict(x, snr_db=z)
+            p = torch.where(k < 0, p, k)
+        return p.clamp_(min=0)
+    return _evaluate_with_confusion(predict, dataloader, device, class_names, save_dir, prefix)

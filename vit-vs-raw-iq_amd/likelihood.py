@@ -21,8 +21,8 @@ There is no CPU path and no backward; `likelihood_reference` is the host fp64 DE
 The phase grid matters: on 128-symbol frames of the 17 classes at 20 dB the host definition classifies 68 of 68 with 64
 rotations and 0.71-0.74 of them with 16 ("Likelihood classifier"), which is why the table is an argument.
 
-Not here: GMSK and OQPSK (not memoryless: no point table), an unknown noise variance (a grid over sigma2), cumulant-based
-classifiers, and the backward.
+Not here: GMSK and OQPSK (not memoryless: no point table) and an unknown noise variance (a grid over sigma2) -- for both see
+cumulants.CumulantClassifier, the feature-based baseline -- and the backward.
 """
 from __future__ import annotations
 

@@ -1,7 +1,7 @@
-"""What the symbol-rate stages share: receiver.Receiver, carrier.Carrier, equaliser.Equaliser and likelihood.LikelihoodClassifier,
-each one HIP launch per direction on a batch of I/Q frames.
+"""What the symbol-rate stages share: receiver.Receiver, carrier.Carrier, equaliser.Equaliser, likelihood.LikelihoodClassifier
+and cumulants.CumulantClassifier, each one HIP launch per direction on a batch of I/Q frames.
 
-Carrier, Equaliser and LikelihoodClassifier derive from `Stage`: frames of a fixed `length` in one of two layouts, whose names
+Carrier, Equaliser, LikelihoodClassifier and CumulantClassifier derive from `Stage`: frames of a fixed `length` in one of two layouts, whose names
 each class keeps in `LAYOUTS`.  A stage writes what is its own: its arguments and tables, `struct()`, its `__call__` (the side
 arguments it takes and the extras it returns), `_forward` / `_backward` (each exactly one C call) and its host fp64 definition.
 Here, once: the per-device table cache (`DeviceTables`, which frontend.FrontEnd uses too), the frame check and the CPU refusal,
