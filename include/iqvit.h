@@ -800,6 +800,68 @@ int iq_frames_likelihood(const float* x, const float* sigma2 /*[n]*/, float* log
                          float* rot_ll /*NULL or [n, C, R]*/, int* best_rot /*NULL or [n, C]*/,
                          int* pred /*NULL or [n]*/, int n_frames, int len,
                          const iq_likelihood_t* par, iq_stream_t stream);
+/* Hybrid likelihood classifier (csrc/likelihood_em.hip): the likelihood test with nothing known.  For every frame and every
+ * candidate constellation the maximum-likelihood complex gain h (amplitude and carrier phase together) and noise variance v, by
+ * expectation-maximisation from a table of starts, the log-likelihood at them, and the class of the largest; |h|^2 / v of that
+ * class is a blind SNR estimate.  x, planar, points and classes are those of iq_frames_likelihood; y_n = I[n] + j Q[n], s_k the M
+ * points of the class.  All arithmetic is fp32, every operation rounded once, in this order; fmaf is the fused multiply-add,
+ * exp2 / log2 the device's base-2 instructions (v_exp_f32, v_log_f32: 1 ulp), every '/' and sqrt is IEEE.  "Over the symbols"
+ * means: lane n % 64 of ONE wave adds its symbols n ascending from +0, then the wave's butterfly (xor 32, 16, 8, 4, 2, 1).
+ *   per class      ss_k = fmaf(Im s_k, Im s_k, Re s_k * Re s_k);  1/M = 1 / (float)M
+ *   per frame      M2 = (over the symbols: fmaf(Im y, Im y, Re y * Re y)) / (float)len;  vfloor = floor * M2
+ *   start t        IQ_EM_TABLE: v = f0 * M2;  a = sqrt(M2 - v);  h = (a * c_t, a * s_t) with starts[t] = (c_t, s_t), two plain numbers
+ *                  IQ_EM_GIVEN: h = h0[b, c], v = v0[b, c], one start (T = 1; starts and n_starts are not looked at)
+ *   a pass at (h, v)
+ *                  q = 1 / v;  q2 = q * LOG2E;  p_k = (fmaf(Re s_k, Re h, -(Im s_k * Im h)), fmaf(Re s_k, Im h, Im s_k * Re h))
+ *                  d_k = fmaf(Im y - Im p_k, Im y - Im p_k, (Re y - Re p_k) * (Re y - Re p_k));  d_min = min_k d_k
+ *                  e_k = exp2(q2 * (d_min - d_k));  S = sum_k e_k, k ascending from +0
+ *   an update pass (iters of them) also forms, k ascending from +0,
+ *                  Wr = fmaf(e_k, Re s_k, Wr), Wi = fmaf(e_k, Im s_k, Wi), Bn = fmaf(e_k, ss_k, Bn), Vn = fmaf(e_k, d_k, Vn);
+ *                  r = 1 / S (once per symbol);  gr = Wr * r;  gi = Wi * r;  and over the symbols
+ *                  Ar = fmaf(Im y, gi, fmaf(Re y, gr, Ar));  Ai = fmaf(-Re y, gi, fmaf(Im y, gr, Ai));  Bq = fmaf(Bn, r, Bq);
+ *                  V = fmaf(Vn, r, V);   then  h' = (Ar / Bq, Ai / Bq);  t = V / (float)len;  v' = t < vfloor ? vfloor : t
+ *                  (the variance from the distances of the pass that formed the responsibilities: an ECM step, which never
+ *                  lowers the likelihood, costs no second pass and does not cancel at high SNR)
+ *   the last pass  l_n = fmaf(-q, d_min, LN2 * log2(S * (1/M)));  L = over the symbols l_n;
+ *                  Lambda = fmaf(-(float)len, LN2 * (LOG2PI + log2(v)), L)  (= L - len ln(pi v): v differs between the classes)
+ * A start whose state, at the start or after an update, is not (h finite, 2^-126 <= v < inf) is DEAD: its Lambda is NaN and it
+ * makes no further pass (a subnormal v counts as no variance: the base-2 logarithm and the division take it for zero).  Over the starts, t ascending, NaNs passed over: the first start with the largest Lambda wins; loglik[b, c] is its
+ * Lambda, (h, v)[b, c] its state after the updates, best_start[b, c] = t.  Where every start's Lambda is NaN (a class of the origin
+ * alone with iters > 0: Bq = 0; a NaN sample; an all-zero frame: M2 = 0) loglik, h and v are NaN and best_start -1: these are data,
+ * never argument errors, and no other (frame, class) is touched.  pred[b] = the first class with the largest loglik[b, c], c
+ * ascending, NaN classes PASSED OVER (one impossible class does not cost the frame its decision); -1 where every class is NaN.
+ * snr_db[b] = TEN_LOG10_2 * log2(fmaf(Im h, Im h, Re h * Re h) / v) of class pred[b]; NaN where pred is -1.
+ * Outputs: loglik fp32 [n_frames, C]; each other NULL or written: h fp32 [n_frames, C, 2], v fp32 [n_frames, C], best_start
+ * int32 [n_frames, C], start_ll fp32 [n_frames, C, T] (every start's Lambda), pred int32 [n_frames] and snr_db fp32 [n_frames],
+ * the last two by a second small launch; snr_db reads h and v, which must then be given.  One workgroup per (frame, class),
+ * classes going out largest first; wave w of four runs the starts t = w, w + 4, ... each through all its passes on its own (no
+ * barrier inside the iteration), the frame and the points in LDS: no atomics, no workspace, two runs agree bit for bit and a
+ * frame's outputs depend on neither n_frames nor its position.  LDS: 28 KB + len * 8 + 4 * M * 8 bytes.  There is no backward.
+ * IQ_STATUS_ARG before any HIP call, outputs untouched: NULL x / loglik / par / points / classes; mode outside IQ_EM_*; NULL starts
+ * or n_starts < 1 (IQ_EM_TABLE); NULL h0 or v0 (IQ_EM_GIVEN); snr_db without h and v; len < 1; n_classes < 1; iters < 0; planar
+ * outside {0,1}; f0 not inside (0, 1) or floor not a finite number >= 0; a class with kind != 0, count < 1, offset < 0 or offset +
+ * count past the int range; x not 8-byte (planar = 0) or 4-byte (planar = 1) aligned, points, h0 and h not 8-byte, any other
+ * pointer not 4-byte aligned.  IQ_STATUS_UNSUPPORTED: C > 64, T > 256, iters > 4096, a class that ends behind point 2048 of the
+ * table, len * 8 bytes above 64 KB, n_frames * C above 2^31 - 1.  n_frames <= 0: success, nothing is launched. */
+enum { IQ_EM_TABLE = 0, IQ_EM_GIVEN = 1 };
+typedef struct iq_likelihood_em {
+  const float* points;                 /* DEVICE fp32 (re, im) pairs, as iq_likelihood_t.points */
+  const iq_synth_class_t* classes;     /* HOST array, copied into the launch; every kind must be 0 */
+  int n_classes;                       /* C in [1, 64] */
+  const float* starts;                 /* DEVICE fp32 [T, 2] = (cos, sin) of the starting phases: plain numbers to the kernel */
+  int n_starts;                        /* T in [1, 256] (IQ_EM_TABLE) */
+  int iters;                           /* updates per start in [0, 4096]; iters + 1 passes */
+  int planar;                          /* 0: x [n, len, 2]; 1: [n, 2, len] */
+  int mode;                            /* IQ_EM_* */
+  float f0;                            /* share of the frame's power the starting variance takes, in (0, 1) */
+  float floor;                         /* the variance never falls below floor * M2; >= 0 */
+  const float* h0;                     /* DEVICE fp32 [n, C, 2]: IQ_EM_GIVEN */
+  const float* v0;                     /* DEVICE fp32 [n, C]: IQ_EM_GIVEN */
+} iq_likelihood_em_t;
+int iq_frames_likelihood_em(const float* x, float* loglik /*[n, C]*/, float* h /*NULL or [n, C, 2]*/, float* v /*NULL or [n, C]*/,
+                            int* best_start /*NULL or [n, C]*/, float* start_ll /*NULL or [n, C, T]*/, int* pred /*NULL or [n]*/,
+                            float* snr_db /*NULL or [n]*/, int n_frames, int len, const iq_likelihood_em_t* par,
+                            iq_stream_t stream);
 /* Cumulant classifier (csrc/cumulants.hip): the feature-based baseline of modulation classification beside the likelihood test
  * (higher-order cumulants in the style of Swami & Sadler).  For every frame the mean, the central moments and the cumulants up to
  * order eight, ten features that no carrier rotation changes, and the weighted distance of the features to every class's

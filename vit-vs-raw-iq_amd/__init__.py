@@ -27,6 +27,9 @@ Import name: `vit_vs_raw_iq_amd` (the directory name contains hyphens; the repo-
                (Equaliser); goes in front of the carrier recovery (Synchronised(equaliser=), ReceivedSynth(equaliser=, carrier=))
   likelihood -- likelihood classifier on the device: the classical AMC baseline over the candidate constellations and a table of
                carrier rotations (LikelihoodClassifier, noise_for); evaluation.evaluate_likelihood_with_confusion writes its report
+  likelihood_em -- hybrid likelihood classifier on the device: the likelihood test with gain, phase and noise unknown, EM per frame
+               and class from a table of starts, and a blind SNR estimate (HybridLikelihoodClassifier);
+               evaluation.evaluate_hybrid_with_confusion writes its report
   cumulants -- cumulant classifier on the device: the feature-based AMC baseline, ten rotation-invariant features of the cumulants
                up to order eight against a centroid per class, blind or with a known noise variance, fitted from generated frames
                (CumulantClassifier); evaluation.evaluate_cumulants_with_confusion writes its report
@@ -53,6 +56,7 @@ from .receiver import (Receiver, ReceivedSynth, mf_table, receiver_reference, re
 from .carrier import Carrier, Synchronised, carrier_reference, carrier_reference_bwd, dft_tables
 from .equaliser import Equaliser, equaliser_reference, equaliser_reference_bwd
 from .likelihood import LikelihoodClassifier, likelihood_reference, noise_for
+from .likelihood_em import HybridLikelihoodClassifier, likelihood_em_reference
 from .cumulants import FEATURE_NAMES, CumulantClassifier, cumulant_features_of, cumulants_reference
 
 __all__ = ["AMCTransformerViT", "AMCTransformerRawIQ", "EncoderViT", "EncoderRawIQ", "EncoderLayer", "LayerNorm",
@@ -65,5 +69,6 @@ __all__ = ["AMCTransformerViT", "AMCTransformerRawIQ", "EncoderViT", "EncoderRaw
            "receiver_reference_bwd", "transmitted_index", "CyclicSpectrum", "cyclic_reference", "cyclic_reference_bwd",
            "Constellation", "constellation_reference", "constellation_reference_bwd", "Carrier", "Synchronised", "carrier_reference",
            "carrier_reference_bwd", "dft_tables", "Equaliser", "equaliser_reference", "equaliser_reference_bwd",
-           "LikelihoodClassifier", "likelihood_reference", "noise_for", "CumulantClassifier", "cumulants_reference",
+           "LikelihoodClassifier", "likelihood_reference", "noise_for", "HybridLikelihoodClassifier",
+           "likelihood_em_reference", "CumulantClassifier", "cumulants_reference",
            "cumulant_features_of", "FEATURE_NAMES"]

@@ -82,6 +82,12 @@ class Likelihood(C.Structure):
                 ("n_rot", C.c_int), ("planar", C.c_int), ("mode", C.c_int), ("gain", C.c_void_p)]
 
 
+class LikelihoodEm(C.Structure):
+    _fields_ = [("points", C.c_void_p), ("classes", C.POINTER(SynthClass)), ("n_classes", C.c_int), ("starts", C.c_void_p),
+                ("n_starts", C.c_int), ("iters", C.c_int), ("planar", C.c_int), ("mode", C.c_int), ("f0", C.c_float),
+                ("floor", C.c_float), ("h0", C.c_void_p), ("v0", C.c_void_p)]
+
+
 class Cumulants(C.Structure):
     _fields_ = [("planar", C.c_int), ("sigma2", C.c_void_p), ("mu", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p),
                 ("n_classes", C.c_int)]
@@ -185,6 +191,7 @@ SIGNATURES = {
     "iq_frames_equalise": (_I, [_P, _P, _P, _P, _I, _I, C.POINTER(Equaliser), _P]),
     "iq_frames_equalise_bwd": (_I, [_P, _P, _I, _I, C.POINTER(Equaliser), _P]),
     "iq_frames_likelihood": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, C.POINTER(Likelihood), _P]),
+    "iq_frames_likelihood_em": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, C.POINTER(LikelihoodEm), _P]),
     "iq_frames_cumulants": (_I, [_P, _P, _P, _P, _P, _I, _I, C.POINTER(Cumulants), _P]),
     "iq_patchify": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "iq_cls_rows": (_I, [_P, _P, _P, _I, _I, _I, C.POINTER(Dropout), _P]),

@@ -153,3 +153,16 @@ def evaluate_cumulants_with_confusion(clf, dataloader: Iterable, device: torch.d
             p = torch.where(k < 0, p, k)
         return p.clamp_(min=0)
     return _evaluate_with_confusion(predict, dataloader, device, class_names, save_dir, prefix)
+
+
+@torch.no_grad()
+def evaluate_hybrid_with_confusion(clf, dataloader: Iterable, device: torch.device, class_names: List[str], save_dir: Path,
+                                   prefix: str = "test") -> Dict:
+    """The same evaluation and the same report file for a likelihood_em.HybridLikelihoodClassifier: a further column for
+    compare_models.py.  `dataloader` yields (frames, labels, snrs) with frames in the classifier's layout; labels index
+    `class_names`, which must be the classifier's classes.  The classifier is handed the frames and nothing else: `snrs` only
+    sorts the results.  A frame no class can explain (pred -1) is counted under class 0."""
+    device = torch.device(device)
+    if list(class_names) != list(clf.class_names):
+        raise ValueError(f"class_names must be the classifier's classes {clf.class_names!r}, got {list(class_names)!r}")
+    return _evaluate_with_confusion(lambda x, y, z: clf.predict(x).clamp_(min=0), dataloader, device, class_names, save_dir, prefix)
