@@ -778,7 +778,7 @@ int iq_frames_equalise_bwd(const float* dout, float* dx, int n_frames, int len, 
  * Outputs: loglik fp32 [n_frames, C]; rot_ll: NULL or fp32 [n_frames, C, R] = L; best_rot: NULL or int32 [n_frames, C]; pred:
  * NULL or int32 [n_frames], written by a second small launch.  One workgroup per (frame, class) runs all R rotations: no atomics,
  * no workspace, two runs agree bit for bit and a frame's outputs depend on neither n_frames nor its position.  LDS 17 KB.
- * There is no backward: nothing downstream differentiates through a log-likelihood.
+ * The backward with respect to x is iq_frames_likelihood_bwd (below); it reads loglik, rot_ll and best_rot as written here.
  * IQ_STATUS_ARG before any HIP call, outputs untouched: NULL x / sigma2 / loglik / par / points / classes / rot; len < 1; n_classes
  * or n_rot < 1; planar outside {0,1}; mode outside IQ_LIK_*; a class with kind != 0, count < 1, offset < 0 or offset + count past
  * the int range; x not 8-byte (planar = 0) or 4-byte (planar = 1) aligned, points not 8-byte, any other pointer not 4-byte aligned.
@@ -836,7 +836,8 @@ int iq_frames_likelihood(const float* x, const float* sigma2 /*[n]*/, float* log
  * the last two by a second small launch; snr_db reads h and v, which must then be given.  One workgroup per (frame, class),
  * classes going out largest first; wave w of four runs the starts t = w, w + 4, ... each through all its passes on its own (no
  * barrier inside the iteration), the frame and the points in LDS: no atomics, no workspace, two runs agree bit for bit and a
- * frame's outputs depend on neither n_frames nor its position.  LDS: 28 KB + len * 8 + 4 * M * 8 bytes.  There is no backward.
+ * frame's outputs depend on neither n_frames nor its position.  LDS: 28 KB + len * 8 + 4 * M * 8 bytes.  The backward with
+ * respect to x at the estimate held fixed is iq_frames_likelihood_em_bwd (below); it reads h and v as written here.
  * IQ_STATUS_ARG before any HIP call, outputs untouched: NULL x / loglik / par / points / classes; mode outside IQ_EM_*; NULL starts
  * or n_starts < 1 (IQ_EM_TABLE); NULL h0 or v0 (IQ_EM_GIVEN); snr_db without h and v; len < 1; n_classes < 1; iters < 0; planar
  * outside {0,1}; f0 not inside (0, 1) or floor not a finite number >= 0; a class with kind != 0, count < 1, offset < 0 or offset +
@@ -862,6 +863,49 @@ int iq_frames_likelihood_em(const float* x, float* loglik /*[n, C]*/, float* h /
                             int* best_start /*NULL or [n, C]*/, float* start_ll /*NULL or [n, C, T]*/, int* pred /*NULL or [n]*/,
                             float* snr_db /*NULL or [n]*/, int n_frames, int len, const iq_likelihood_em_t* par,
                             iq_stream_t stream);
+/* Gradients of the two likelihood classifiers with respect to the frame (csrc/likelihood_bwd.hip): given dloglik[b, c], the
+ * gradient of a scalar with respect to loglik, dx[b, n] = d(sum_c dloglik[b, c] loglik[b, c]) / d(Re y_n, Im y_n) with everything
+ * else held fixed: sigma2, gain, the points and the rotation table, the winning rotation (IQ_LIK_MAX: the true gradient wherever
+ * the maximum is unique) and the EM estimate (h, v) (at a converged interior EM point also the total derivative: the estimate
+ * maximises the likelihood it is put into).  It is the soft symbol decision: for one hypothesis of one class
+ * d l_n / d(Re y, Im y) = -2 q (y - m), m = sum_k e_k p_k / S with e_k and S the forward's.  x, planar, points, classes, rot and
+ * gain are the forward's, dx has x's layout.  All arithmetic is fp32, every operation rounded once, in this order; '/' is IEEE.
+ *   dx[b, n]       = the sum, from +0, over c ascending and within a class over t ascending, of the terms below; a (class,
+ *                  hypothesis) whose weight w is exactly 0 is SKIPPED, and so is a whole class whose dloglik[b, c] is exactly 0
+ *                  before anything of it is read: a one-class gradient or the {-1, +1} of a margin loss costs the classes it
+ *                  touches, and a NaN in the results of a class nobody asked about stays out of dx
+ * iq_frames_likelihood_bwd, with q, q2, a, p_k, 1/M, y', d_k, d_min exactly as iq_frames_likelihood forms them:
+ *   hypotheses     IQ_LIK_MAX: t = best_rot[b, c] alone, w = dloglik[b, c] (a best_rot outside [0, R) with a nonzero dloglik:
+ *                  NaN in dx[b], nothing is read through it);  IQ_LIK_MEAN: every r,
+ *                  w = (dloglik[b, c] * exp2(LOG2E * (rot_ll[b, c, r] - loglik[b, c]))) * (1 / (float)R): the rotation's share
+ *                  (no reduction: loglik is the log of the mean already)
+ *   per symbol     e_k = exp2(q2 * (d_min - d_k));  S = S + e_k, Wr = fmaf(e_k, Re p_k, Wr), Wi = fmaf(e_k, Im p_k, Wi), k ascending
+ *                  from +0;  r = 1 / S;  m = (Wr * r, Wi * r);  wq = w * (-2 * q);  g = (wq * (Re y' - Re m), wq * (Im y' - Im m))
+ *   back to y      t = (fmaf(Re g, c_r, -(Im g * s_r)), fmaf(Re g, s_r, Im g * c_r));  dx = (Re dx + Re t, Im dx + Im t)
+ * iq_frames_likelihood_em_bwd, one hypothesis (h, v)[b, c] per class, with q, q2, p_k, d_k, d_min, e_k, S as a pass of
+ * iq_frames_likelihood_em forms them at that state:
+ *   per symbol     Wr, Wi, r and m as above;  wq = dloglik[b, c] * (-2 * q);
+ *                  dx = (fmaf(wq, Re y - Re m, Re dx), fmaf(wq, Im y - Im m, Im dx))
+ * The term -len log(pi v) does not depend on y.  Data, not arguments: a frame whose sigma2 the forward refuses gets NaN in all of
+ * its dx; a (frame, class) with a nonzero dloglik whose state is not (h finite, 2^-126 <= v < inf) -- the forward's NaN -- gets NaN
+ * in all of its frame's dx; nothing else is touched, and other NaNs stay within their symbol.  iq_frames_likelihood_em_bwd reads
+ * points, classes, n_classes and planar of its struct and IGNORES starts, n_starts, iters, mode, f0, floor, h0 and v0.
+ * One workgroup per (frame, 512 symbols), a lane two symbols with their dx in registers over all classes and hypotheses: no
+ * cross-lane reduction, no atomics, no workspace; two runs agree bit for bit and a symbol's dx depends on neither n_frames nor
+ * the frame's position.  LDS 16 KB.  One launch each.
+ * IQ_STATUS_ARG before any HIP call, dx untouched: NULL x / dloglik / dx / par / points / classes, NULL sigma2 / rot (likelihood),
+ * NULL h / v (EM); NULL best_rot in IQ_LIK_MAX; NULL loglik or rot_ll in IQ_LIK_MEAN; len < 1; n_classes < 1; n_rot < 1, mode
+ * outside IQ_LIK_* (likelihood); planar outside {0,1}; a class with kind != 0, count < 1, offset < 0 or offset + count past the int
+ * range; x or dx not 8-byte (planar = 0) or 4-byte (planar = 1) aligned, points and h not 8-byte, any other pointer not 4-byte
+ * aligned.  IQ_STATUS_UNSUPPORTED: C > 64, R > 256, a class that ends behind point 2048 of the table, len * 8 bytes above 64 KB,
+ * n_frames * ceil(len / 512) above 2^31 - 1.  n_frames <= 0: success, nothing is launched. */
+int iq_frames_likelihood_bwd(const float* x, const float* sigma2 /*[n]*/, const float* dloglik /*[n, C]*/,
+                             const float* loglik /*[n, C]: IQ_LIK_MEAN*/, const float* rot_ll /*[n, C, R]: IQ_LIK_MEAN*/,
+                             const int* best_rot /*[n, C]: IQ_LIK_MAX*/, float* dx /*x's layout*/, int n_frames, int len,
+                             const iq_likelihood_t* par, iq_stream_t stream);
+int iq_frames_likelihood_em_bwd(const float* x, const float* dloglik /*[n, C]*/, const float* h /*[n, C, 2]*/,
+                                const float* v /*[n, C]*/, float* dx /*x's layout*/, int n_frames, int len,
+                                const iq_likelihood_em_t* par, iq_stream_t stream);
 /* Cumulant classifier (csrc/cumulants.hip): the feature-based baseline of modulation classification beside the likelihood test
  * (higher-order cumulants in the style of Swami & Sadler).  For every frame the mean, the central moments and the cumulants up to
  * order eight, ten features that no carrier rotation changes, and the weighted distance of the features to every class's

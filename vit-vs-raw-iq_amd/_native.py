@@ -192,6 +192,8 @@ SIGNATURES = {
     "iq_frames_equalise_bwd": (_I, [_P, _P, _I, _I, C.POINTER(Equaliser), _P]),
     "iq_frames_likelihood": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, C.POINTER(Likelihood), _P]),
     "iq_frames_likelihood_em": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, C.POINTER(LikelihoodEm), _P]),
+    "iq_frames_likelihood_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, C.POINTER(Likelihood), _P]),
+    "iq_frames_likelihood_em_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, C.POINTER(LikelihoodEm), _P]),
     "iq_frames_cumulants": (_I, [_P, _P, _P, _P, _P, _I, _I, C.POINTER(Cumulants), _P]),
     "iq_patchify": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "iq_cls_rows": (_I, [_P, _P, _P, _I, _I, _I, C.POINTER(Dropout), _P]),

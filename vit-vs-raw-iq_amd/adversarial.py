@@ -16,6 +16,17 @@ backward() of an earlier forward raises afterwards, as after any later forward. 
 
 eps and alpha are in the units of the model's input, the z-scored frame (data.py): one unit is one standard deviation of the
 channel.  clip = (lo, hi) bounds every element after each step (None or a None bound: unbounded).
+
+The classical columns.  `model` may be a likelihood.LikelihoodClassifier or a likelihood_em.HybridLikelihoodClassifier: src is
+then a batch of device frames in the classifier's layout, and every step is the classifier's forward, d loss / d loglik, its
+backward (iq_frames_likelihood_bwd / iq_frames_likelihood_em_bwd: the forward runs once per step) and the same iq_linf_step.
+Keywords of that path only: the classifier's noise (sigma2= | snr_db=, gain=; the hybrid takes none) and
+  loss="margin" (the default)   max_{c != y} loglik_c - loglik_y: -1 at the label, +1 at the first largest other class.  At 20 dB
+                                the classes lie 10 to several hundred nats apart, so softmax - onehot is exactly zero in fp32
+                                for most frames and the cross entropy has no gradient to follow; the margin always has one.
+  loss="ce"                     iq_ce_fwd_bwd on loglik as logits, as the model path.
+There eps and alpha are in the FRAME's own units (a unit-power signal for the generators' frames), not in z-score units: the
+model path's eps is eps_model = eps_frame / std of the channel.
 """
 from __future__ import annotations
 
@@ -26,7 +37,11 @@ import operator
 import torch
 
 from . import _native as N
+from .likelihood import LikelihoodClassifier
+from .likelihood_em import HybridLikelihoodClassifier
 from .saliency import _batch, _ce_grad, _classes, _forward, _input_grad, _resolve
+
+LOSSES = ("margin", "ce")                    # of the classifier path
 
 
 def _nonneg(v, what):
@@ -72,7 +87,84 @@ def _attack(plan, src, lab, eps, alpha, steps, start, lo, hi, batch):
     return out
 
 
-def fgsm(model, src, labels, eps, clip=None, batch=256):
+# ---- the likelihood classifiers in place of a model
+
+def _is_classifier(model):
+    return isinstance(model, (LikelihoodClassifier, HybridLikelihoodClassifier))
+
+
+def _model_only(loss, noise):
+    """The model path takes neither keyword of the classifier path."""
+    if loss is not None or noise:
+        raise TypeError(f"loss= and the noise keywords belong to the likelihood classifiers, not to a model: got "
+                        f"{sorted(noise) + (['loss'] if loss is not None else [])}")
+
+
+def _clf_prepare(clf, src, labels, batch, loss, noise):
+    """-> (frames contiguous fp32, labels on their device, the classifier's side arguments for the whole batch, batch, loss)"""
+    loss = "margin" if loss is None else loss
+    if loss not in LOSSES:
+        raise ValueError(f"loss must be one of {LOSSES}, got {loss!r}")
+    if loss == "margin" and clf.n_classes < 2:
+        raise ValueError("loss='margin' needs at least two classes")
+    batch = _batch(batch)
+    n = src.shape[0] if isinstance(src, torch.Tensor) and src.dim() > 0 else 0
+    lab = _classes(labels, n, clf.n_classes, "labels")
+    side = clf._check(src, **noise)                        # shape, noise and device, in the classifier's words
+    return src.detach().contiguous().float(), lab.to(src.device), side, batch, loss
+
+
+def _margin_grad(loglik, labels):
+    """d (max_{c != y} loglik_c - loglik_y) / d loglik: -1 at the label, +1 at the first largest other class."""
+    at = labels[:, None]
+    other = loglik.scatter(1, at, float("-inf")).argmax(1, keepdim=True)
+    return torch.zeros_like(loglik).scatter_(1, at, -1.0).scatter_(1, other, 1.0)
+
+
+def _clf_ce_grad(loglik, labels):
+    dl = torch.empty_like(loglik)
+    B, K = loglik.shape
+    N.check(N.lib().iq_ce_fwd_bwd(N.ptr(loglik), N.ptr(labels), B, K, 0.0, 1.0, None, None, N.ptr(dl), N.stream_handle()),
+            "iq_ce_fwd_bwd")
+    return dl
+
+
+def _chunk(side, i, batch):
+    return tuple(None if t is None else t[i:i + batch].contiguous() for t in side)
+
+
+def _clf_attack(clf, src, lab, side, eps, alpha, steps, start, lo, hi, batch, loss):
+    out = start
+    with torch.no_grad():
+        for i in range(0, src.shape[0], batch):
+            x0, xa, y, args = src[i:i + batch], out[i:i + batch], lab[i:i + batch].contiguous(), _chunk(side, i, batch)
+            for _ in range(steps):
+                outs, held = clf._forward(xa, *args)
+                loglik = outs[0].contiguous()
+                dl = _margin_grad(loglik, y) if loss == "margin" else _clf_ce_grad(loglik, y)
+                _step(xa, clf._backward(xa, dl, *held), x0, alpha, eps, lo, hi)
+    return out
+
+
+def _random_start(src, eps, seed, lo, hi):
+    g = torch.Generator(device=src.device)
+    g.manual_seed(seed)
+    noise = torch.rand(src.shape, generator=g, device=src.device, dtype=torch.float32).mul_(2 * eps).sub_(eps)
+    start = torch.minimum(torch.maximum(src + noise, src - eps), src + eps)
+    if lo == lo:
+        start.clamp_(min=lo)
+    if hi == hi:
+        start.clamp_(max=hi)
+    return start
+
+
+def fgsm(model, src, labels, eps, clip=None, batch=256, loss=None, **noise):
+    if _is_classifier(model):
+        eps = _nonneg(eps, "eps")
+        lo, hi = _clip(clip)
+        src, lab, side, batch, loss = _clf_prepare(model, src, labels, batch, loss, noise)      # (the device refusal comes last)
+        return _clf_attack(model, src, lab, side, eps, eps, 1, src.clone(), lo, hi, batch, loss)
+    _model_only(loss, noise)
     enc, plan_of, lab, batch = _prepare(model, src, labels, batch)
     eps = _nonneg(eps, "eps")
     lo, hi = _clip(clip)
@@ -81,7 +173,16 @@ def fgsm(model, src, labels, eps, clip=None, batch=256):
     return _attack(plan, src, lab.to(src.device), eps, eps, 1, src.clone(), lo, hi, batch)
 
 
-def pgd(model, src, labels, eps, alpha, steps, random_start=False, seed=0, clip=None, batch=256):
+def pgd(model, src, labels, eps, alpha, steps, random_start=False, seed=0, clip=None, batch=256, loss=None, **noise):
+    if _is_classifier(model):
+        eps, alpha, steps, seed = _nonneg(eps, "eps"), _nonneg(alpha, "alpha"), operator.index(steps), operator.index(seed)
+        if steps < 1:
+            raise ValueError(f"steps must be >= 1, got {steps}")
+        lo, hi = _clip(clip)
+        src, lab, side, batch, loss = _clf_prepare(model, src, labels, batch, loss, noise)
+        start = _random_start(src, eps, seed, lo, hi) if random_start and eps > 0 else src.clone()
+        return _clf_attack(model, src, lab, side, eps, alpha, steps, start, lo, hi, batch, loss)
+    _model_only(loss, noise)
     enc, plan_of, lab, batch = _prepare(model, src, labels, batch)
     eps = _nonneg(eps, "eps")
     alpha = _nonneg(alpha, "alpha")
@@ -92,16 +193,7 @@ def pgd(model, src, labels, eps, alpha, steps, random_start=False, seed=0, clip=
     lo, hi = _clip(clip)
     src = enc._expect(src)
     plan = plan_of()
-    start = src.clone()
-    if random_start and eps > 0:
-        g = torch.Generator(device=src.device)
-        g.manual_seed(seed)
-        noise = torch.rand(src.shape, generator=g, device=src.device, dtype=torch.float32).mul_(2 * eps).sub_(eps)
-        start = torch.minimum(torch.maximum(src + noise, src - eps), src + eps)
-        if lo == lo:
-            start.clamp_(min=lo)
-        if hi == hi:
-            start.clamp_(max=hi)
+    start = _random_start(src, eps, seed, lo, hi) if random_start and eps > 0 else src.clone()
     return _attack(plan, src, lab.to(src.device), eps, alpha, steps, start, lo, hi, batch)
 
 
@@ -110,6 +202,8 @@ def robustness_curve(model, x, y, eps_list, attack="fgsm", batch=256, **kw):
         raise ValueError(f"attack must be 'fgsm' or 'pgd', got {attack!r}")
     eps_list = [_nonneg(e, "eps") for e in eps_list]
     allowed = {"clip"} if attack == "fgsm" else {"clip", "alpha", "steps", "random_start", "seed"}
+    if _is_classifier(model):
+        allowed |= {"loss", "sigma2", "snr_db", "gain"}
     extra = set(kw) - allowed
     if extra:
         raise TypeError(f"unexpected keyword arguments for attack={attack!r}: {sorted(extra)}")
@@ -119,6 +213,8 @@ def robustness_curve(model, x, y, eps_list, attack="fgsm", batch=256, **kw):
     if kw.get("alpha") is not None:
         _nonneg(kw["alpha"], "alpha")
     _clip(kw.get("clip"))
+    if _is_classifier(model):
+        return _clf_curve(model, x, y, eps_list, attack, batch, steps, kw)
     enc, plan_of, lab, batch = _prepare(model, x, y, batch)
     x = enc._expect(x)
     plan = plan_of()
@@ -143,3 +239,38 @@ def robustness_curve(model, x, y, eps_list, attack="fgsm", batch=256, **kw):
             out.append(accuracy(pgd(model, x, lab, eps, alpha, steps, random_start=kw.get("random_start", False),
                                     seed=kw.get("seed", 0), clip=kw.get("clip"), batch=batch)))
     return out
+
+
+def _clf_pred(clf, x, side):
+    """The decisions alone (int32), of frames and side arguments that are checked already."""
+    if isinstance(clf, LikelihoodClassifier):
+        return clf._launch(x, *side, False, False, True)[3]
+    return clf._launch(x, *side, False, True)[5]
+
+
+def _clf_curve(clf, x, y, eps_list, attack, batch, steps, kw):
+    """robustness_curve of a likelihood classifier: the accuracy is that of clf.predict under the same noise keywords."""
+    noise = {k: kw[k] for k in ("sigma2", "snr_db", "gain") if k in kw}
+    x, lab, side, batch, loss = _clf_prepare(clf, x, y, batch, kw.get("loss"), noise)
+
+    def accuracy(xs):
+        correct = torch.zeros((), dtype=torch.int64, device=x.device)
+        with torch.no_grad():
+            for i in range(0, xs.shape[0], batch):
+                pred = _clf_pred(clf, xs[i:i + batch], _chunk(side, i, batch))
+                correct += (pred == lab[i:i + batch]).sum()
+        return correct.item() / max(1, xs.shape[0])
+
+    out = []
+    for eps in eps_list:
+        if eps == 0:
+            out.append(accuracy(x))
+        elif attack == "fgsm":
+            out.append(accuracy(fgsm(clf, x, lab, eps, clip=kw.get("clip"), batch=batch, loss=loss, **noise)))
+        else:
+            alpha = kw.get("alpha")
+            alpha = 2.5 * eps / steps if alpha is None else alpha
+            out.append(accuracy(pgd(clf, x, lab, eps, alpha, steps, random_start=kw.get("random_start", False),
+                                    seed=kw.get("seed", 0), clip=kw.get("clip"), batch=batch, loss=loss, **noise)))
+    return out
+

@@ -12,17 +12,25 @@ then over the rotations their maximum (mode 'max', the GLRT) or the log of their
 largest.  The term -len log(pi sigma2) is common to all classes and left out.  The definition with every rounding is written out in
 include/iqvit.h.  The work is B R len sum_c M_c evaluations of a distance and an exponential -- 1.4e10 at B = 256, len = 1024,
 R = 64 and the 812 points of the 17 table classes -- which torch broadcasting would materialise as a B x R x len x M tensor.
-There is no CPU path and no backward; `likelihood_reference` is the host fp64 DEFINITION the tests compare against.
+There is no CPU path; `likelihood_reference` is the host fp64 DEFINITION the tests compare against.
 
-  LikelihoodClassifier(length, classes, rotations, mode, layout)     clf(x, sigma2= | snr_db=, gain=) -> loglik (B, C)
+  LikelihoodClassifier(length, classes, rotations, mode, layout, differentiable)     clf(x, sigma2= | snr_db=, gain=) -> loglik (B, C)
   clf.predict(...) -> (B,) int64        clf.class_names          noise_for(snr_db, normalised) -> (gain, sigma2)
+  clf.input_gradient(x, dloglik, sigma2= | snr_db=, gain=) -> dx       d <dloglik, loglik> / d x, the shape of x
+
+The gradient with respect to the frame (csrc/likelihood_bwd.hip, iq_frames_likelihood_bwd) is the soft symbol decision:
+-2 q (y - m) per hypothesis, m the posterior mean of the scaled points, summed over the classes by dloglik and over the rotations by
+their shares ('mean') or at the winning rotation alone ('max': the true gradient wherever the maximum is unique).  With
+differentiable=True, clf(x, ...) returns loglik on the autograd graph of x, so that Receiver -> Equaliser -> Carrier -> classifier
+carries x.grad down to the raw frame; adversarial.fgsm / pgd / robustness_curve take the classifier in place of a model.
   likelihood_reference(x, sigma2, gain, points, classes, angles, mode) -> loglik, per-rotation table, best_rot, pred
 
 The phase grid matters: on 128-symbol frames of the 17 classes at 20 dB the host definition classifies 68 of 68 with 64
 rotations and 0.71-0.74 of them with 16 ("Likelihood classifier"), which is why the table is an argument.
 
 Not here: GMSK and OQPSK (not memoryless: no point table) and an unknown noise variance (a grid over sigma2) -- for both see
-cumulants.CumulantClassifier, the feature-based baseline -- and the backward.
+cumulants.CumulantClassifier, the feature-based baseline -- and gradients with respect to sigma2, gain, the points or the
+rotation table.
 """
 from __future__ import annotations
 
@@ -81,18 +89,52 @@ def rotation_table(angles):
     return np.stack([np.cos(ang), np.sin(ang)], axis=1).astype(np.float32)
 
 
+class _LoglikFn(torch.autograd.Function):
+    """loglik = clf(x), differentiable with respect to x with the forward's per-(frame, class) results held fixed.  The classifier
+    (LikelihoodClassifier, likelihood_em.HybridLikelihoodClassifier) supplies
+      _forward(x, *args) -> (loglik, *extras), held     the forward's C call (x contiguous fp32); held: what the backward reads,
+                                                        tensors or None
+      _backward(x, dloglik, *held) -> dx                the one C call
+    -> (loglik, *extras); the extras are marked non-differentiable."""
+
+    @staticmethod
+    def forward(ctx, x, clf, *args):
+        x = x.detach().contiguous().float()
+        outs, held = clf._forward(x, *args)
+        ctx.clf = clf
+        ctx.save_for_backward(x, *held)
+        ctx.mark_non_differentiable(*[t for t in outs[1:] if t is not None])      # all in ONE call
+        return outs
+
+    @staticmethod
+    def backward(ctx, dloglik, *_):
+        x, *held = ctx.saved_tensors
+        return (ctx.clf._backward(x, dloglik.contiguous().float(), *held),) + (None,) * (len(ctx.needs_input_grad) - 1)
+
+
+def _dloglik(dloglik, x, n_classes):
+    """The (B, C) gradient argument of input_gradient: a tensor, fp32 and contiguous on x's device."""
+    if not isinstance(dloglik, torch.Tensor) or dloglik.dtype.is_complex or dloglik.dtype == torch.bool:
+        raise TypeError(f"dloglik must be a tensor of real numbers, got {dloglik!r}")
+    if tuple(dloglik.shape) != (x.shape[0], n_classes):
+        raise ValueError(f"dloglik must have shape {(x.shape[0], n_classes)}: one value per frame and class, got {tuple(dloglik.shape)}")
+    return dloglik.detach().to(device=x.device, dtype=torch.float32).contiguous()
+
+
 class LikelihoodClassifier(Stage):
     """Frames of `length` symbols at one sample per symbol -> the log-likelihood of each of the classes.  classes: names
     data.constellation knows (default: its 17, in data.CLASSES' order), (name, points) pairs or {name: points} for constellations
     of one's own, scaled to unit mean power in fp64 and rounded to the fp32 table as FrameSynth does.  rotations: a count R
     (angles 2 pi r / R, the full circle) or an array of angles in radians.  mode: 'max' or 'mean' over the rotations.  layout:
-    'frames' (B, length, 2) or 'planar' (B, 2, length).  A call runs on the device its x lies on.  Arguments are checked here,
+    'frames' (B, length, 2) or 'planar' (B, 2, length).  differentiable: a call returns loglik on the autograd graph of x (the
+    extras are not differentiable); False: x is detached.  A call runs on the device its x lies on.  Arguments are checked here,
     before any device work."""
 
     LAYOUTS, reference = LAYOUTS, "likelihood_reference"
 
-    def __init__(self, length, classes=None, rotations=64, mode: str = "max", layout: str = "frames"):
+    def __init__(self, length, classes=None, rotations=64, mode: str = "max", layout: str = "frames", differentiable=False):
         super().__init__(length, layout)
+        self.differentiable = _flag(differentiable, "differentiable")
         if classes is None:
             classes = TABLE_CLASSES
         if isinstance(classes, str):
@@ -149,7 +191,7 @@ class LikelihoodClassifier(Stage):
         return N.Likelihood(points=points, classes=self._classes_c, n_classes=self.n_classes, rot=rot, n_rot=self.n_rotations,
                             planar=self.planar, mode=MODES.index(self.mode), gain=gain)
 
-    def _check(self, x, sigma2, snr_db, gain):
+    def _check(self, x, sigma2=None, snr_db=None, gain=None):
         self._check_shape(x)
         if (sigma2 is None) == (snr_db is None):
             raise ValueError("pass the noise as sigma2= (the variance per frame) or as snr_db= (generator convention): one of them")
@@ -164,7 +206,9 @@ class LikelihoodClassifier(Stage):
 
     def _run(self, x, sigma2, snr_db, gain, want_rot, want_best, want_pred):
         sigma2, gain = self._check(x, sigma2, snr_db, gain)
-        x = x.detach().contiguous().float()
+        return self._launch(x.detach().contiguous().float(), sigma2, gain, want_rot, want_best, want_pred)
+
+    def _launch(self, x, sigma2, gain, want_rot, want_best, want_pred):
         B, d, Cn, R = x.shape[0], x.device, self.n_classes, self.n_rotations
         loglik = torch.empty(B, Cn, dtype=torch.float32, device=d)
         rot_ll = torch.empty(B, Cn, R, dtype=torch.float32, device=d) if want_rot else None
@@ -178,6 +222,35 @@ class LikelihoodClassifier(Stage):
                                                  torch.cuda.current_stream(d).cuda_stream), "iq_frames_likelihood")
         return loglik, rot_ll, best, pred
 
+    def _forward(self, x, sigma2, gain, want_rot=False, want_best=False):
+        """_LoglikFn's forward: the extras asked for, and held = (sigma2, gain, loglik, rot_ll, best_rot), of the last three what
+        the mode's backward reads."""
+        mean = self.mode == "mean"
+        loglik, rot_ll, best, _ = self._launch(x, sigma2, gain, want_rot or mean, want_best or not mean, False)
+        return (loglik, rot_ll if want_rot else None, best if want_best else None), \
+            (sigma2, gain, loglik if mean else None, rot_ll if mean else None, None if mean else best)
+
+    def _backward(self, x, dloglik, sigma2, gain, loglik, rot_ll, best):
+        dx = torch.empty_like(x)
+        if x.shape[0] > 0:
+            points, rot = self.table_on(x.device, ("points", "rot"))
+            par = self.struct(points.data_ptr(), rot.data_ptr(), N.ptr(gain))
+            N.check(N.lib().iq_frames_likelihood_bwd(x.data_ptr(), sigma2.data_ptr(), dloglik.data_ptr(), N.ptr(loglik), N.ptr(rot_ll),
+                                                     N.ptr(best), dx.data_ptr(), x.shape[0], self.length, C.byref(par),
+                                                     torch.cuda.current_stream(x.device).cuda_stream), "iq_frames_likelihood_bwd")
+        return dx
+
+    def input_gradient(self, x, dloglik, sigma2=None, snr_db=None, gain=None):
+        """d <dloglik, loglik> / d x: x and the noise as in a call, dloglik (B, C) a tensor (a one-hot row: that class's
+        gradient; a class with weight 0 costs nothing).  -> dx, the shape of x, fp32.  Two C calls (the forward for what the
+        backward reads, then the backward) on the current stream, no autograd and no host synchronisation."""
+        self._check_shape(x)
+        dloglik = _dloglik(dloglik, x, self.n_classes)
+        sigma2, gain = self._check(x, sigma2, snr_db, gain)
+        x = x.detach().contiguous().float()
+        with torch.no_grad():
+            return self._backward(x, dloglik, *self._forward(x, sigma2, gain)[1])
+
     def __call__(self, x, sigma2=None, snr_db=None, gain=None, return_rot=False, return_best=False):
         """x: device frames in this classifier's layout, fp32; the noise as sigma2 (variance E|w|^2 per frame: a number or B
         values) or as snr_db (generator convention: noise_for(snr_db)); gain: the amplitude of the constellation in the frame
@@ -185,6 +258,8 @@ class LikelihoodClassifier(Stage):
         table (B, C, R) fp32 and best_rot (B, C) int32, the first rotation that attains the maximum.  A frame whose sigma2 is
         not a positive finite number gets NaN (best_rot -1)."""
         return_rot, return_best = _flag(return_rot, "return_rot"), _flag(return_best, "return_best")
+        if self.differentiable:
+            return pack(*_LoglikFn.apply(x, self, *self._check(x, sigma2, snr_db, gain), return_rot, return_best))
         loglik, rot_ll, best, _ = self._run(x, sigma2, snr_db, gain, return_rot, return_best, False)
         return pack(loglik, rot_ll, best)
 
@@ -196,7 +271,7 @@ class LikelihoodClassifier(Stage):
 
     def __repr__(self):
         return (f"LikelihoodClassifier(length={self.length}, classes={self.class_names!r}, rotations={self.n_rotations}, "
-                f"mode={self.mode!r}, layout={self.layout!r})")
+                f"mode={self.mode!r}, layout={self.layout!r}{', differentiable=True' if self.differentiable else ''})")
 
 
 # ---- the host definition

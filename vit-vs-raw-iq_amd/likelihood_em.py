@@ -10,18 +10,25 @@ variance v by expectation-maximisation (EM) from a table of starting phases, and
 One HIP kernel (csrc/likelihood_em.hip, iq_frames_likelihood_em) runs all starts and all iterations of a (frame, class) inside
 one workgroup, one EM chain per wave; the definition with every rounding is written out in include/iqvit.h.  |h|^2 / v of the
 winning class is a blind SNR estimate, and (v, |h|) are what LikelihoodClassifier(sigma2=, gain=) and
-CumulantClassifier(sigma2=) were missing.  There is no CPU path and no backward; `likelihood_em_reference` is the host fp64
-DEFINITION the tests compare against.
+CumulantClassifier(sigma2=) were missing.  There is no CPU path; `likelihood_em_reference` is the host fp64 DEFINITION the tests
+compare against.
 
-  HybridLikelihoodClassifier(length, classes, starts, iters, init_noise, floor, layout)     clf(x) -> Lambda (B, C)
+  HybridLikelihoodClassifier(length, classes, starts, iters, init_noise, floor, layout, differentiable)     clf(x) -> Lambda (B, C)
   clf.predict(x) -> (B,) int64        clf.estimate(x) -> (pred, snr_db, sigma2, gain)        clf.class_names
+  clf.input_gradient(x, dloglik) -> dx       d <dloglik, Lambda> / d x with the estimate (h, v) held fixed, the shape of x
+
+The gradient with respect to the frame (csrc/likelihood_bwd.hip, iq_frames_likelihood_em_bwd) holds the estimate fixed, as the
+receiver holds its timing and the equaliser its weights: -(2 / v) (y - m), m the posterior mean of h s_k.  At a converged interior
+EM point that is also the total derivative (the estimate maximises the likelihood it is put into).  differentiable=True puts
+clf(x) on the autograd graph of x; adversarial.fgsm / pgd / robustness_curve take the classifier in place of a model.
   likelihood_em_reference(x, points, classes, starts, iters, init_noise, floor, h0, v0) -> EmReference
 
 The defaults (16 starts, 32 iterations, a starting noise share of 0.02) are from the host sweep in DESIGN.md, "Hybrid likelihood
 classifier": the iteration count and the starting variance matter a great deal, the number of starts beyond 16 does not.
 
 Not here: pruning the starts, a class-dependent start table, a convergence test in place of a fixed `iters`, GMSK and OQPSK (no
-point table), a frequency offset inside the model (carrier.Carrier comes first), the backward.
+point table), a frequency offset inside the model (carrier.Carrier comes first), differentiating through the EM iterations,
+gradients with respect to the points.
 """
 from __future__ import annotations
 
@@ -33,7 +40,7 @@ import torch
 
 from . import _native as N
 from ._args import _flag, _index, _number
-from .likelihood import LAYOUTS, MAX_ROTATIONS, LikelihoodClassifier, _rotation_angles, rotation_table
+from .likelihood import LAYOUTS, MAX_ROTATIONS, LikelihoodClassifier, _dloglik, _LoglikFn, _rotation_angles, rotation_table
 from .stage import Stage, _first_largest, _frames, _host, no_cpu, pack, reals
 
 MAX_STARTS, MAX_ITERS = MAX_ROTATIONS, 4096             # the limits of iq_frames_likelihood_em (its classes: iq_frames_likelihood's)
@@ -54,13 +61,16 @@ class HybridLikelihoodClassifier(Stage):
     complex gain and the noise variance.  classes: as LikelihoodClassifier's (whose table and checks these are).  starts: a count
     T (phases 2 pi t / T) or an array of phases in radians.  iters: EM updates per start.  init_noise: the share f0 of the frame's
     power the starting variance takes (the starting amplitude takes the rest).  floor: the variance never falls below floor times
-    the frame's power.  layout: 'frames' (B, length, 2) or 'planar' (B, 2, length).  A call runs on the device its x lies on.
-    Arguments are checked here, before any device work."""
+    the frame's power.  layout: 'frames' (B, length, 2) or 'planar' (B, 2, length).  differentiable: a call returns Lambda on the
+    autograd graph of x with the estimate held fixed (the extras are not differentiable); False: x is detached.  A call runs on the
+    device its x lies on.  Arguments are checked here, before any device work."""
 
     LAYOUTS, reference = LAYOUTS, "likelihood_em_reference"
 
-    def __init__(self, length, classes=None, starts=16, iters=32, init_noise=0.02, floor=1e-6, layout: str = "frames"):
+    def __init__(self, length, classes=None, starts=16, iters=32, init_noise=0.02, floor=1e-6, layout: str = "frames",
+                 differentiable=False):
         super().__init__(length, layout)
+        self.differentiable = _flag(differentiable, "differentiable")
         table = LikelihoodClassifier(length, classes, rotations=1, layout=layout)         # the class and point handling: not restated
         self.class_names, self.descriptors, self.points = table.class_names, table.descriptors, table.points
         self._classes_c = table._classes_c
@@ -87,7 +97,7 @@ class HybridLikelihoodClassifier(Stage):
                               iters=self.iters, planar=self.planar, mode=int(h0 is not None), f0=self.init_noise, floor=self.floor,
                               h0=h0, v0=v0)
 
-    def _check(self, x, h0, v0):
+    def _check(self, x, h0=None, v0=None):
         self._check_shape(x)
         if (h0 is None) != (v0 is None):
             raise ValueError("pass both h0 (B, C, 2) and v0 (B, C), the start of every (frame, class), or neither")
@@ -101,7 +111,9 @@ class HybridLikelihoodClassifier(Stage):
 
     def _run(self, x, h0=None, v0=None, want_starts=False, want_pred=False):
         h0, v0 = self._check(x, h0, v0)
-        x = x.detach().contiguous().float()
+        return self._launch(x.detach().contiguous().float(), h0, v0, want_starts, want_pred)
+
+    def _launch(self, x, h0, v0, want_starts, want_pred):
         B, d, Cn, T = x.shape[0], x.device, self.n_classes, 1 if h0 is not None else self.n_starts
         new = lambda *shape, dtype=torch.float32: torch.empty(*shape, dtype=dtype, device=d)           # noqa: E731
         loglik, h, v, best = new(B, Cn), new(B, Cn, 2), new(B, Cn), new(B, Cn, dtype=torch.int32)
@@ -115,6 +127,32 @@ class HybridLikelihoodClassifier(Stage):
                                                     torch.cuda.current_stream(d).cuda_stream), "iq_frames_likelihood_em")
         return loglik, h, v, best, start_ll, pred, snr
 
+    def _forward(self, x, h0=None, v0=None, want_starts=False):
+        """_LoglikFn's forward: (Lambda, h, v, best_start, start_ll) and held = (h, v), what the backward reads."""
+        loglik, h, v, best, start_ll, _, _ = self._launch(x, h0, v0, want_starts, False)
+        return (loglik, h, v, best, start_ll), (h, v)
+
+    def _backward(self, x, dloglik, h, v):
+        dx = torch.empty_like(x)
+        if x.shape[0] > 0:
+            par = self.struct(self.table_on(x.device, "points").data_ptr())
+            N.check(N.lib().iq_frames_likelihood_em_bwd(x.data_ptr(), dloglik.data_ptr(), h.data_ptr(), v.data_ptr(), dx.data_ptr(),
+                                                        x.shape[0], self.length, C.byref(par),
+                                                        torch.cuda.current_stream(x.device).cuda_stream), "iq_frames_likelihood_em_bwd")
+        return dx
+
+    def input_gradient(self, x, dloglik, h0=None, v0=None):
+        """d <dloglik, Lambda> / d x with the estimate (h, v) of every (frame, class) held fixed: x, h0 and v0 as in a call,
+        dloglik (B, C) a tensor (a class with weight 0 costs nothing, and a dead class with weight 0 leaves dx finite).  -> dx, the
+        shape of x, fp32.  Two C calls (the forward for (h, v), then the backward) on the current stream, no autograd and no host
+        synchronisation."""
+        self._check_shape(x)
+        dloglik = _dloglik(dloglik, x, self.n_classes)
+        h0, v0 = self._check(x, h0, v0)
+        x = x.detach().contiguous().float()
+        with torch.no_grad():
+            return self._backward(x, dloglik, *self._forward(x, h0, v0)[1])
+
     def __call__(self, x, h0=None, v0=None, return_estimates=False, return_starts=False):
         """x: device frames in this classifier's layout, fp32.  h0 (B, C, 2) (or complex (B, C)) and v0 (B, C): the start of every
         (frame, class), a single one in place of the table (a warm start from the frame before).  -> Lambda (B, C) fp32 on the
@@ -122,7 +160,10 @@ class HybridLikelihoodClassifier(Stage):
         then, with return_starts, every start's Lambda (B, C, T).  A (frame, class) whose every start leaves the finite, positive
         states (a class of the origin alone, a NaN sample, an all-zero frame) gets NaN (best_start -1)."""
         return_estimates, return_starts = _flag(return_estimates, "return_estimates"), _flag(return_starts, "return_starts")
-        loglik, h, v, best, start_ll, _, _ = self._run(x, h0, v0, return_starts)
+        if self.differentiable:
+            loglik, h, v, best, start_ll = _LoglikFn.apply(x, self, *self._check(x, h0, v0), return_starts)
+        else:
+            loglik, h, v, best, start_ll, _, _ = self._run(x, h0, v0, return_starts)
         return pack(loglik, *((h, v, best) if return_estimates else ()), start_ll)
 
     def predict(self, x):
@@ -142,7 +183,8 @@ class HybridLikelihoodClassifier(Stage):
 
     def __repr__(self):
         return (f"HybridLikelihoodClassifier(length={self.length}, classes={self.class_names!r}, starts={self.n_starts}, "
-                f"iters={self.iters}, init_noise={self.init_noise}, floor={self.floor}, layout={self.layout!r})")
+                f"iters={self.iters}, init_noise={self.init_noise}, floor={self.floor}, layout={self.layout!r}"
+                f"{', differentiable=True' if self.differentiable else ''})")
 
 
 # ---- the host definition
