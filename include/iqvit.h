@@ -944,7 +944,8 @@ int iq_frames_likelihood_em_bwd(const float* x, const float* dloglik /*[n, C]*/,
  * other frame is touched.
  * Outputs, each NULL or: feat fp32 [n_frames, 10]; mom fp32 [n_frames, 20]; score fp32 [n_frames, C]; pred int32 [n_frames].  One
  * launch.  No atomics, no workspace, two runs agree bit for bit and a frame's outputs depend on neither n_frames nor its
- * position.  LDS: the frame, len * 8 bytes (four frames on the wave route), and 304 bytes.  There is no backward.
+ * position.  LDS: the frame, len * 8 bytes (four frames on the wave route), and 304 bytes.  The backward with respect to x is
+ * iq_frames_cumulants_bwd (below); it reads none of these outputs.
  * IQ_STATUS_ARG before any HIP call, outputs untouched: NULL x / par; all four outputs NULL; len < 1; planar outside {0,1};
  * n_classes < 0; n_classes > 0 with NULL mu or w; score or pred with n_classes == 0; x not 8-byte (planar = 0) or 4-byte
  * (planar = 1) aligned, any other pointer not 4-byte aligned.
@@ -961,6 +962,55 @@ typedef struct iq_cumulants {
 int iq_frames_cumulants(const float* x, float* feat /*NULL or [n,10]*/, float* mom /*NULL or [n,20]*/,
                         float* score /*NULL or [n,C]*/, int* pred /*NULL or [n]*/,
                         int n_frames, int len, const iq_cumulants_t* par, iq_stream_t stream);
+/* Gradient of the cumulant classifier with respect to the frame (csrc/cumulants_bwd.hip): dx[b, n] = dL / d(Re y_n, Im y_n) of
+ * L = sum_c dscore[b, c] score[b, c] + sum_f dfeat[b, f] feat[b, f], with sigma2, mu, w and bias held fixed and NOTHING else: the
+ * true gradient, through the mean and through P.  x, planar, sigma2, mu, w and n_classes are the forward's (bias is not read), dx
+ * has x's layout; dscore NULL: the classes are not looked at; dfeat NULL: 0.  Self-contained: m, the moments, the cumulants, P,
+ * P2, P3, P4 and feat are formed again from the frame exactly as iq_frames_cumulants forms them, bit for bit; no forward output is
+ * read.  A complex gradient is G = dL/dRe + j dL/dIm.  Beside the forward's notation: s u is (s * u.re, s * u.im),
+ * u + v the two sums, u / s the two IEEE divisions, <u, v> = fmaf(u.re, v.re, u.im * v.im) = Re(conj(u) v); all fp32, every
+ * operation rounded once, in this order:
+ *   gf[0..9]       = dfeat[b, f] (NULL: +0); then for c ascending, a class whose dscore[b, c] is exactly 0 SKIPPED before anything
+ *                  of it is read (a NaN row of mu of a class nobody asked about stays out):
+ *                  gf[f] = fmaf((-2 * dscore[b, c]) * w[c, f], feat[f] - mu[c, f], gf[f])
+ *   gP             = -(acc / P), acc from +0, f ascending: acc = fmaf(k_f * feat[f], gf[f], acc), k = 1 1 2 2 2 3 3 3 3 4
+ *   gm             = ((gf[0] + gf[0]) / P) m
+ *   mag(g, C, Pk)  = (g / (|C| * Pk)) C, and (0, 0) where |C| is exactly 0 (the subgradient; |C| as the forward rounds it)
+ *                  gC20 = mag(gf[1], M20, P); gC40 = mag(gf[2], C40, P2); gC41 = mag(gf[3], C41, P2); gC42 = gf[4] / P2;
+ *                  gC60 = mag(gf[5], C60, P3); gC61 = mag(gf[6], C61, P3); gC62 = mag(gf[7], C62, P3); gC63 = gf[8] / P3;
+ *                  gC80 = mag(gf[9], C80, P4)
+ *   moments        the chain rule on the closed forms above, each line left to right; a term s u + acc is the forward's fused pair
+ *                  G60 = -28 (conj(M20) gC80) + gC60
+ *                  G42 = fmaf(-(9 * M21), gC63, fmaf(-6, <gC62, M20>, gC42))
+ *                  G41 = (-6 * gC63) M20 + (-(8 * M21) gC62 + (-10 (conj(M20) gC61) + gC41))
+ *                  G40 = (-1 (M20 gC62) + (-(5 * M21) gC61 + (-15 (conj(M20) gC60) + gC40))) + conj(420 q + (-70 M40)) gC80
+ *                  G21 = fmaf(-(4 * M21), gC42, fmaf(-3, <gC41, M20>, gP));  G21 = G21 + <gC61, 30 q + (-5 M40)>;
+ *                        G21 = G21 + <gC62, (48 * M21) M20 + (-8 M41)>;
+ *                        G21 = fmaf(gC63, fmaf(18, n, fmaf(36 * M21, M21, -9 * M42)), G21)
+ *                  G20 = -(gC42 + gC42) M20 + (-(3 * M21) gC41 + (-6 (conj(M20) gC40) + gC20));
+ *                        G20 = G20 + conj(90 q + (-15 M40)) gC60;  G20 = G20 + conj((60 * M21) M20 + (-10 M41)) gC61;
+ *                        G20 = fmaf(24 * M21, M21, fmaf(12, n, -6 * M42)) gC62 + G20;  G20 = G20 + conj(gC62) (6 q + (-M40));
+ *                        G20 = gC63 ((36 * M21) M20 + (-6 M41)) + G20;
+ *                        G20 = G20 + conj(-2520 (q M20) + (840 (M20 M40) + (-28 M60))) gC80
+ *                  G61 = gC61, G62 = gC62, G63 = gC63, G80 = gC80
+ *   coefficients   H = G / (float)len;  A20 = 2 H20, A21 = 2 * H21, A40 = 4 H40, A41 = 3 H41, B41 = conj(H41), A42 = 4 * H42,
+ *                  A60 = 6 H60, A61 = 5 H61, B61 = conj(H61), A62 = 4 H62, B62 = conj(2 H62), A63 = 6 * H63, A80 = 8 H80
+ *   per symbol     z, z2, z4, r, r2 as the forward; z3 = z2 z, z5 = z4 z, z7 = z4 z3;
+ *                  k1 = r2 A62 + (r A41 + A20);  kz = fmaf(r2, A63, fmaf(r, A42, A21));  k3 = r A61 + A40;  k3b = r B62 + B41;
+ *                  g = conj(z) k1;  g = kz z + g;  then g = g + t for t = conj(z3) k3 | z3 k3b | conj(z5) A60 | z5 B61 | conj(z7) A80
+ *   sum g          in the forward's order of sums (the lane's symbols ascending from +0, the butterfly, the four waves)
+ *   dx[b, n]       = g_n + (gm / (float)len - sum g / (float)len), each part
+ * Data, not arguments: a frame whose P the forward refuses gets NaN in all of its dx; no other frame is touched.
+ * One launch, the forward's two routes by the length alone; a thread touches only the LDS slots it wrote.  No atomics, no
+ * workspace; two runs agree bit for bit and a frame's dx depends on neither n_frames nor its position.  LDS: the frame, len * 8
+ * bytes (four frames on the wave route), and 336 bytes.
+ * IQ_STATUS_ARG before any HIP call, dx untouched: NULL x / dx / par; dscore and dfeat both NULL; len < 1; planar outside {0,1};
+ * n_classes < 0; n_classes > 0 with NULL mu or w; dscore with n_classes == 0; x or dx not 8-byte (planar = 0) or 4-byte
+ * (planar = 1) aligned, any other pointer not 4-byte aligned.
+ * IQ_STATUS_UNSUPPORTED: C > 64, len * 8 bytes above 64 KB, n_frames * max(C, 20) above 2^31 - 1.  n_frames <= 0: success, nothing
+ * is launched. */
+int iq_frames_cumulants_bwd(const float* x, const float* dscore /*NULL or [n, C]*/, const float* dfeat /*NULL or [n, 10]*/,
+                            float* dx /*x's layout*/, int n_frames, int len, const iq_cumulants_t* par, iq_stream_t stream);
 int iq_patchify(const float* src, void* patches, int kind, int B, int C, int H, int W, int p, int Kpad,
                 iq_stream_t stream);
 int iq_cls_rows(const float* cls, const float* pe, void* x0, int B, int S, int D, const iq_dropout_t* drop,

@@ -32,7 +32,8 @@ Import name: `vit_vs_raw_iq_amd` (the directory name contains hyphens; the repo-
                evaluation.evaluate_hybrid_with_confusion writes its report
   cumulants -- cumulant classifier on the device: the feature-based AMC baseline, ten rotation-invariant features of the cumulants
                up to order eight against a centroid per class, blind or with a known noise variance, fitted from generated frames
-               (CumulantClassifier); evaluation.evaluate_cumulants_with_confusion writes its report
+               (CumulantClassifier), and the true gradient of its scores and features with respect to the symbols;
+               evaluation.evaluate_cumulants_with_confusion writes its report
   _native   -- ctypes binding of include/iqvit.h  (libiqvit.so; no fallback)
   ViT.models.amc_transformer / transformer_rawIQ.models.transformer_rawIQ
             -- import paths used by the reference's scripts (hyperparameter_tuning.py:19,37)
@@ -44,7 +45,7 @@ from ._native import IqError, LIB_PATH
 from .attention_maps import attention_maps, attention_rollout, rollout_to_input
 from .saliency import input_gradient, integrated_gradients
 from .relevance import attention_relevance, grad_attention_maps
-from .adversarial import fgsm, pgd, robustness_curve
+from .adversarial import fgsm, pgd, robustness_curve, transfer_table
 from .impairments import Impairments, impair, impair_reference, impairment_curve
 from .synth import FrameSynth, SynthStream, synth_reference, train_on_stream
 from .waveform import ShapedSynth, gmsk_table, rrc_table, waveform_reference
@@ -57,18 +58,18 @@ from .carrier import Carrier, Synchronised, carrier_reference, carrier_reference
 from .equaliser import Equaliser, equaliser_reference, equaliser_reference_bwd
 from .likelihood import LikelihoodClassifier, likelihood_reference, noise_for
 from .likelihood_em import HybridLikelihoodClassifier, likelihood_em_reference
-from .cumulants import FEATURE_NAMES, CumulantClassifier, cumulant_features_of, cumulants_reference
+from .cumulants import FEATURE_NAMES, CumulantClassifier, cumulant_features_of, cumulants_reference, cumulants_reference_bwd
 
 __all__ = ["AMCTransformerViT", "AMCTransformerRawIQ", "EncoderViT", "EncoderRawIQ", "EncoderLayer", "LayerNorm",
            "MultiHeadAttention", "PositionwiseFeedForward", "ScaleDotProductAttention", "PatchEmbedding",
            "SequenceEmbedding", "NativePlan", "IqError", "LIB_PATH", "attention_maps", "attention_rollout",
            "rollout_to_input", "input_gradient", "integrated_gradients", "attention_relevance", "grad_attention_maps", "fgsm",
-           "pgd", "robustness_curve", "Impairments", "impair", "impair_reference", "impairment_curve", "FrameSynth",
+           "pgd", "robustness_curve", "transfer_table", "Impairments", "impair", "impair_reference", "impairment_curve", "FrameSynth",
            "SynthStream", "synth_reference", "train_on_stream", "Spectrogram", "spectrogram_reference", "spectrogram_reference_bwd",
            "ShapedSynth", "rrc_table", "gmsk_table", "waveform_reference", "Receiver", "ReceivedSynth", "mf_table", "receiver_reference",
            "receiver_reference_bwd", "transmitted_index", "CyclicSpectrum", "cyclic_reference", "cyclic_reference_bwd",
            "Constellation", "constellation_reference", "constellation_reference_bwd", "Carrier", "Synchronised", "carrier_reference",
            "carrier_reference_bwd", "dft_tables", "Equaliser", "equaliser_reference", "equaliser_reference_bwd",
            "LikelihoodClassifier", "likelihood_reference", "noise_for", "HybridLikelihoodClassifier",
-           "likelihood_em_reference", "CumulantClassifier", "cumulants_reference",
+           "likelihood_em_reference", "CumulantClassifier", "cumulants_reference", "cumulants_reference_bwd",
            "cumulant_features_of", "FEATURE_NAMES"]

@@ -195,6 +195,7 @@ SIGNATURES = {
     "iq_frames_likelihood_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, C.POINTER(Likelihood), _P]),
     "iq_frames_likelihood_em_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, C.POINTER(LikelihoodEm), _P]),
     "iq_frames_cumulants": (_I, [_P, _P, _P, _P, _P, _I, _I, C.POINTER(Cumulants), _P]),
+    "iq_frames_cumulants_bwd": (_I, [_P, _P, _P, _P, _I, _I, C.POINTER(Cumulants), _P]),
     "iq_patchify": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "iq_cls_rows": (_I, [_P, _P, _P, _I, _I, _I, C.POINTER(Dropout), _P]),
     "iq_embed_bwd_gather": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, C.POINTER(Dropout), _I, _P]),

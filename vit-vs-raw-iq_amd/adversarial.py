@@ -17,16 +17,23 @@ backward() of an earlier forward raises afterwards, as after any later forward. 
 eps and alpha are in the units of the model's input, the z-scored frame (data.py): one unit is one standard deviation of the
 channel.  clip = (lo, hi) bounds every element after each step (None or a None bound: unbounded).
 
-The classical columns.  `model` may be a likelihood.LikelihoodClassifier or a likelihood_em.HybridLikelihoodClassifier: src is
-then a batch of device frames in the classifier's layout, and every step is the classifier's forward, d loss / d loglik, its
-backward (iq_frames_likelihood_bwd / iq_frames_likelihood_em_bwd: the forward runs once per step) and the same iq_linf_step.
-Keywords of that path only: the classifier's noise (sigma2= | snr_db=, gain=; the hybrid takes none) and
+The classical columns.  `model` may be a likelihood.LikelihoodClassifier, a likelihood_em.HybridLikelihoodClassifier or a
+cumulants.CumulantClassifier: src is then a batch of device frames in the classifier's layout, and every step is the classifier's
+forward, d loss / d loglik (the cumulant classifier's scores stand for loglik), its backward (iq_frames_likelihood_bwd /
+iq_frames_likelihood_em_bwd / iq_frames_cumulants_bwd: the forward runs once per step) and the same iq_linf_step.
+Keywords of that path only: the classifier's noise (sigma2= | snr_db=, gain=; the hybrid takes none; the cumulant classifier
+takes sigma2= | snr_db= or neither, and no gain) and
   loss="margin" (the default)   max_{c != y} loglik_c - loglik_y: -1 at the label, +1 at the first largest other class.  At 20 dB
                                 the classes lie 10 to several hundred nats apart, so softmax - onehot is exactly zero in fp32
                                 for most frames and the cross entropy has no gradient to follow; the margin always has one.
   loss="ce"                     iq_ce_fwd_bwd on loglik as logits, as the model path.
 There eps and alpha are in the FRAME's own units (a unit-power signal for the generators' frames), not in z-score units: the
 model path's eps is eps_model = eps_frame / std of the channel.
+
+  transfer_table(sources, targets, x, y, eps, attack="fgsm", **kw)     accuracies (len(sources) + 1, len(targets)): row 0 clean,
+                                                              row i + 1 the frames crafted against sources[i], judged by
+                                                              every target (a classifier, (classifier, {noise keywords}) or a
+                                                              callable frames -> predictions)
 """
 from __future__ import annotations
 
@@ -37,6 +44,7 @@ import operator
 import torch
 
 from . import _native as N
+from .cumulants import CumulantClassifier
 from .likelihood import LikelihoodClassifier
 from .likelihood_em import HybridLikelihoodClassifier
 from .saliency import _batch, _ce_grad, _classes, _forward, _input_grad, _resolve
@@ -87,10 +95,10 @@ def _attack(plan, src, lab, eps, alpha, steps, start, lo, hi, batch):
     return out
 
 
-# ---- the likelihood classifiers in place of a model
+# ---- the classical classifiers in place of a model
 
 def _is_classifier(model):
-    return isinstance(model, (LikelihoodClassifier, HybridLikelihoodClassifier))
+    return isinstance(model, (LikelihoodClassifier, HybridLikelihoodClassifier, CumulantClassifier))
 
 
 def _model_only(loss, noise):
@@ -110,7 +118,8 @@ def _clf_prepare(clf, src, labels, batch, loss, noise):
     batch = _batch(batch)
     n = src.shape[0] if isinstance(src, torch.Tensor) and src.dim() > 0 else 0
     lab = _classes(labels, n, clf.n_classes, "labels")
-    side = clf._check(src, **noise)                        # shape, noise and device, in the classifier's words
+    check = clf._side if isinstance(clf, CumulantClassifier) else clf._check
+    side = check(src, **noise)                             # shape, noise and device, in the classifier's words
     return src.detach().contiguous().float(), lab.to(src.device), side, batch, loss
 
 
@@ -245,21 +254,27 @@ def _clf_pred(clf, x, side):
     """The decisions alone (int32), of frames and side arguments that are checked already."""
     if isinstance(clf, LikelihoodClassifier):
         return clf._launch(x, *side, False, False, True)[3]
+    if isinstance(clf, CumulantClassifier):
+        return clf._launch(x, *side, False, False, False, True)[3]
     return clf._launch(x, *side, False, True)[5]
 
 
+def _clf_accuracy(clf, xs, lab, side, batch):
+    correct = torch.zeros((), dtype=torch.int64, device=xs.device)
+    with torch.no_grad():
+        for i in range(0, xs.shape[0], batch):
+            pred = _clf_pred(clf, xs[i:i + batch], _chunk(side, i, batch))
+            correct += (pred == lab[i:i + batch]).sum()
+    return correct.item() / max(1, xs.shape[0])
+
+
 def _clf_curve(clf, x, y, eps_list, attack, batch, steps, kw):
-    """robustness_curve of a likelihood classifier: the accuracy is that of clf.predict under the same noise keywords."""
+    """robustness_curve of a classical classifier: the accuracy is that of clf.predict under the same noise keywords."""
     noise = {k: kw[k] for k in ("sigma2", "snr_db", "gain") if k in kw}
     x, lab, side, batch, loss = _clf_prepare(clf, x, y, batch, kw.get("loss"), noise)
 
     def accuracy(xs):
-        correct = torch.zeros((), dtype=torch.int64, device=x.device)
-        with torch.no_grad():
-            for i in range(0, xs.shape[0], batch):
-                pred = _clf_pred(clf, xs[i:i + batch], _chunk(side, i, batch))
-                correct += (pred == lab[i:i + batch]).sum()
-        return correct.item() / max(1, xs.shape[0])
+        return _clf_accuracy(clf, xs, lab, side, batch)
 
     out = []
     for eps in eps_list:
@@ -274,3 +289,81 @@ def _clf_curve(clf, x, y, eps_list, attack, batch, steps, kw):
                                     seed=kw.get("seed", 0), clip=kw.get("clip"), batch=batch, loss=loss, **noise)))
     return out
 
+
+def _party(item, what, callable_ok):
+    """A source or target of transfer_table -> (classifier or callable, its noise keywords)."""
+    clf, noise = item if isinstance(item, tuple) and len(item) == 2 and isinstance(item[1], dict) else (item, {})
+    if _is_classifier(clf):
+        return clf, dict(noise)
+    if callable_ok and not noise and callable(clf) and not isinstance(clf, tuple):
+        return clf, None
+    raise TypeError(f"{what} must be a LikelihoodClassifier, a HybridLikelihoodClassifier or a CumulantClassifier, or a pair "
+                    f"(classifier, {{its noise keywords}}){', or a callable frames -> (B,) predictions' if callable_ok else ''}, "
+                    f"got {item!r}")
+
+
+def transfer_table(sources, targets, x, y, eps, attack="fgsm", batch=256, **kw):
+    """Does a perturbation crafted against one classical classifier fool the others?  -> a (len(sources) + 1, len(targets)) list
+    of rows of top-1 accuracies: row 0 the clean frames, row i + 1 the frames `attack` ("fgsm" | "pgd", with robustness_curve's
+    keywords and PGD defaults, loss= among them) crafted at `eps` against sources[i], each judged by every target.  A source is
+    a classical classifier or (classifier, {its noise keywords}); a target is either of those or any callable frames -> (B,)
+    predictions (a model behind its own input layout).  All classifiers share length and layout, which is checked with every
+    other argument before any device work.  Each source is attacked once, not once per target; a classifier target's accuracy
+    is clf.predict's under its own keywords, so a diagonal entry is that classifier's robustness_curve entry."""
+    if attack not in ("fgsm", "pgd"):
+        raise ValueError(f"attack must be 'fgsm' or 'pgd', got {attack!r}")
+    eps = _nonneg(eps, "eps")
+    extra = set(kw) - ({"clip", "loss"} if attack == "fgsm" else {"clip", "loss", "alpha", "steps", "random_start", "seed"})
+    if extra:
+        raise TypeError(f"unexpected keyword arguments for attack={attack!r}: {sorted(extra)}")
+    steps = operator.index(kw.get("steps", 10))
+    if steps < 1:
+        raise ValueError(f"steps must be >= 1, got {steps}")
+    alpha = 2.5 * eps / steps if kw.get("alpha") is None else _nonneg(kw["alpha"], "alpha")
+    _clip(kw.get("clip"))
+    sources, targets = list(sources), list(targets)
+    if not sources or not targets:
+        raise ValueError("sources and targets must not be empty")
+    src = [_party(s, "a source", False) for s in sources]
+    tgt = [_party(t, "a target", True) for t in targets]
+    clfs = [c for c, noise in src + tgt if noise is not None]
+    for c in clfs[1:]:
+        if (c.length, c.layout) != (clfs[0].length, clfs[0].layout):
+            raise ValueError(f"all classifiers must share length and layout: {clfs[0]!r} against {c!r}")
+    batch = _batch(batch)
+    # every keyword of every party is checked before the first launch; the refusal of CPU frames, each party's last check,
+    # comes after the other parties' checks too
+    refused, prepared, judges = None, [], []
+    for i, (c, noise) in enumerate(src + tgt):
+        attacked = i < len(src)
+        out = None
+        if noise is not None:
+            try:
+                out = _clf_prepare(c, x, y, batch, kw.get("loss") if attacked else "ce", noise)     # (a judge has no loss)
+            except N.IqError as e:
+                refused = refused or e
+        (prepared if attacked else judges).append(out)
+    if refused is not None:
+        raise refused
+    x0, labels = prepared[0][:2]
+
+    def judge(xs):
+        row = []
+        for (c, noise), held in zip(tgt, judges):
+            if noise is None:
+                with torch.no_grad():
+                    pred = torch.as_tensor(c(xs)).to(xs.device)
+                row.append((pred == labels).sum().item() / max(1, xs.shape[0]))
+            else:
+                row.append(_clf_accuracy(c, xs, held[1], held[2], batch))
+        return row
+
+    table = [judge(x0)]
+    for (c, noise), (xs, lab, _, _, loss) in zip(src, prepared):
+        if attack == "fgsm":
+            adv = fgsm(c, xs, lab, eps, clip=kw.get("clip"), batch=batch, loss=loss, **noise)
+        else:
+            adv = pgd(c, xs, lab, eps, alpha, steps, random_start=kw.get("random_start", False), seed=kw.get("seed", 0),
+                      clip=kw.get("clip"), batch=batch, loss=loss, **noise)
+        table.append(judge(adv))
+    return table

@@ -91,7 +91,7 @@ def rotation_table(angles):
 
 class _LoglikFn(torch.autograd.Function):
     """loglik = clf(x), differentiable with respect to x with the forward's per-(frame, class) results held fixed.  The classifier
-    (LikelihoodClassifier, likelihood_em.HybridLikelihoodClassifier) supplies
+    (LikelihoodClassifier, likelihood_em.HybridLikelihoodClassifier; cumulants.CumulantClassifier, which holds sigma2 alone) supplies
       _forward(x, *args) -> (loglik, *extras), held     the forward's C call (x contiguous fp32); held: what the backward reads,
                                                         tensors or None
       _backward(x, dloglik, *held) -> dx                the one C call
