@@ -41,6 +41,8 @@ typedef struct iq_dropout {
 #define IQ_SITE_IMPAIR 0xFFFFFFFFu
 /* The value below it is RESERVED too: the `site` counter word of the synthetic frame source (iq_frames_synth). */
 #define IQ_SITE_SYNTH 0xFFFFFFFEu
+/* And the next: the `site` counter word of the fading channel (iq_frames_fade). */
+#define IQ_SITE_FADE 0xFFFFFFFDu
 
 /* ---------------------------------------------------------------------------------------
  * LayerNorm.  Replaces LayerNorm.forward, V/models/layers/layers_norm.py:11-19 (eps 1e-12,
@@ -442,6 +444,86 @@ typedef struct iq_waveform {
 int iq_frames_waveform(float* raw /*[n,len,2]*/, int64_t* labels, float* snr, float* drawn /*NULL or [n,8]*/,
                        int32_t* symbols /*NULL or [n,NS]*/, float* taps /*NULL or [n,8,2]*/, int n_frames, int len,
                        const iq_waveform_t* par, iq_stream_t stream);
+/* Fading channel (csrc/fading.hip): taps whose gains move with a Doppler spread, read at positions that drift with a sample-clock
+ * offset.  It works on any raw frames: x[n_frames, len_in, 2] fp32 -> y[n_frames, len_out, 2] fp32; x[m] = x[m][0] + j x[m][1]
+ * is zero outside [0, len_in) (a select supplies the zero, never a read).  L = n_taps, NS = n_sin.
+ * Positions are int64 in units of 2^-32 sample; there is no floating-point time anywhere.
+ *   P[n] = T0 + n S, n = 0 .. len_out-1; S = 2^32 + d, d the clock drift (int32), T0 the start.
+ *   Tap l reads at Q = P[n] - (delay[l] << 16); delay[l] >= 0 is an int32 in units of 2^-16 sample.
+ *   m = Q >> 32 (arithmetic: the floor, also of a negative Q); f = ((Q & 0xFFFFFFFF) * n_frac) >> 32, in [0, n_frac).
+ * Interpolation: interp is a DEVICE fp32 [n_frac][K] table, plain numbers to the kernel (fading.py fills it with a Kaiser-windowed
+ * sinc); c = (K - 1) / 2 (integer division).
+ *   r_l[n] = sum_{k < K} x[m + k - c] interp[f][k]: the product of k = 0, then fmaf over k = 1 .. K-1 ascending, real and
+ *   imaginary parts separately.
+ * Tap gains: tap l is a sum of NS + 1 paths, path 0 the line of sight, paths 1 .. NS the scatterers.  phase and inc are int32 in
+ * units of 2^-32 turn (per sample); phase + n inc wraps and is exact until the one conversion iq_frames_waveform and
+ * iq_frames_carrier use: e(p) = (cos, sin)(pi x), x = (float)(int32)p * 2^-31 (sincospif).
+ *   g_l[n] = sum_s amp[l][s] e(phase[l][s] + n inc[l][s]): from +0, fmaf(amp, cos, re) and fmaf(amp, sin, im), s = 0 .. NS
+ *   ascending; a path whose amp is exactly 0 is skipped (an unused slot costs nothing and may hold anything).
+ * Output: y[n] = sum_l rot(r_l[n], g_l[n]): from +0, one rounded addition per component and tap, l ascending; rot(v, c, s) = v (c +
+ * j s) = (fmaf(v.re, c, -(v.im * s)), fmaf(v.re, s, v.im * c)) as in iq_frames_carrier.  Then the generators' tail: P = mean
+ * |y|^2 (thread n % 256 its samples ascending, fmaf(im, im, fmaf(re, re, acc)), the wave's butterfly, the four wave sums in order);
+ * normalise = 1: y / sqrt(P + 1e-12) as a product with the rounded reciprocal; snr_db NULL or DEVICE fp32 [n_frames]: where it is
+ * given and not NaN, complex AWGN of sigma = sqrt(0.5 * 10^(-snr/10)) per component is added, i.e. at that SNR relative to unit
+ * power (with normalise = 0 the caller's frames should have unit power for the figure to be an SNR).
+ * Random numbers: key and counter layout of iq_frames_synth with the site IQ_SITE_FADE: key = (low word of seed, high word of
+ * seed ^ high word of j), counter = (c, low word of j, IQ_SITE_FADE, stream), j = frame_base + i.  A frame is a pure function of
+ * (seed, stream, j) and of its own input.
+ *   c = 0x80000000 + p: the noise of samples 2p and 2p+1, as in iq_frames_synth (both modes).
+ *   IQ_FADE_DRAWN only:
+ *   c = 0xFFFFFFFF: word 0: d = d_lo + umulhi(w, d_hi - d_lo + 1); word 1: T0 = (start << 32) + (timing ? w : 0); word 2: the
+ *       frame's maximum Doppler fd = min(fmaf(fd_hi - fd_lo, (w >> 8) 2^-24, fd_lo), fd_hi) cycles per sample in fp32, converted
+ *       once: fd_inc = rint(fd * 2^32) (exact in double).  Word 3 is not used.
+ *   c = 0xFFFFF000 + 33 l + s, l < L, s <= NS: path s of tap l.  word 0: phase[l][s] for s >= 1 (the raw word); the line of sight
+ *       has phase 0 at n = 0 (the frame's carrier phase belongs to the generator, and a channel without Doppler, drift and
+ *       scatterers is then the identity).  word 1: u = (w >> 8) 2^-24, inc[l][s] = rint(fd_inc * (double)cos) wrapped to int32,
+ *       cos the fp32 cosine of sincospif(2 u): Clarke's model, a random arrival angle per path.
+ *   amp[l][0] = los[l]; amp[l][s] = tap_sigma[l] * sqrtf(2.f / NS) (one rounded fp32 product) for 1 <= s <= NS: with tap_sigma the
+ *       per-component deviation as in iq_waveform_t, E|g_l|^2 = los^2 + 2 tap_sigma^2.  Every other slot is (0, 0), amp 0.
+ * IQ_FADE_GIVEN: paths int32 [n_frames, 8, 33, 2] = (phase, inc), amps fp32 [n_frames, 8, 33] and clock int64 [n_frames, 2] =
+ * {T0, S} are the caller's (S as given: the caller keeps T0 + n S inside an int64); only slots l < L, s <= NS are looked at;
+ * nothing is drawn but the noise.
+ * Outputs: paths_out, amps_out, clock_out: NULL or arrays of those shapes: what the frame used (either mode).
+ * With L = 1, NS = 0, los = 1, fd = 0, d = 0, start = 0, timing = 0, K = n_frac = 1, interp = {1.0}, normalise = 0 and no noise,
+ * len_out = len_in: y = x bit for bit (but a negative zero may come back positive).
+ * One workgroup of 256 threads per frame; both frames, the interpolation table and the path table lie in LDS, the output until
+ * its power is known.  Lanes split samples, never paths: every sum is in loop order.  No atomics, no workspace: two runs agree
+ * bit for bit, and a frame's output depends on neither n_frames nor its position.  Nothing is allocated, nothing synchronises.
+ * IQ_STATUS_ARG before any launch, outputs untouched: NULL x / y / par / interp; mode outside IQ_FADE_*; NULL paths / amps / clock
+ * with IQ_FADE_GIVEN; len_out or len_in below 1; n_taps, K or n_frac below 1; n_sin < 0; normalise or timing outside {0,1}; for a
+ * tap l < L a negative delay or a non-finite or negative los or tap_sigma; a non-finite or negative fd_lo or fd_hi; fd_hi > 0.5;
+ * fd_lo > fd_hi; d_lo > d_hi (or a range of all 2^32 values); x, y, paths, paths_out, clock, clock_out not 8-byte aligned, any
+ * other pointer not 4-byte aligned.  IQ_STATUS_UNSUPPORTED: n_taps > 8, n_sin > 32, K > 16, n_frac > 256; len_in * 8 or len_out * 8
+ * bytes above 64 KB; frames plus tables above the CU's 160 KB of LDS (with the limits above the largest case takes 147.1 KB, so
+ * this one cannot trigger today).  n_frames <= 0: success, nothing is launched. */
+enum { IQ_FADE_GIVEN = 0, IQ_FADE_DRAWN = 1 };
+typedef struct iq_fading {
+  int mode;                /* IQ_FADE_* */
+  int len_in;              /* samples of an input frame */
+  int n_taps;              /* L, 1..8 */
+  int n_sin;               /* NS: scatterers per tap, 0..32 */
+  int K;                   /* interpolation taps, 1..16 */
+  int n_frac;              /* fractional phases in the table, 1..256 */
+  int normalise;           /* 1: unit mean power */
+  int timing;              /* DRAWN: 1: a fractional start drawn per frame */
+  const float* interp;     /* DEVICE fp32 [n_frac][K] */
+  const float* snr_db;     /* NULL or DEVICE fp32 [n_frames]; NaN: no noise for that frame */
+  const int32_t* paths;    /* GIVEN: DEVICE int32 [n_frames,8,33,2] = (phase, inc) */
+  const float* amps;       /* GIVEN: DEVICE fp32 [n_frames,8,33] */
+  const int64_t* clock;    /* GIVEN: DEVICE int64 [n_frames,2] = {T0, S} */
+  int32_t delay[8];        /* tap delays, units of 2^-16 sample, >= 0 */
+  float los[8];            /* DRAWN: amplitude of the line of sight of tap l */
+  float tap_sigma[8];      /* DRAWN: per-component deviation of the scatter of tap l */
+  float fd_lo, fd_hi;      /* DRAWN: maximum Doppler ~ U[lo,hi] cycles per sample, 0 <= lo <= hi <= 0.5 */
+  int32_t d_lo, d_hi;      /* DRAWN: clock drift d uniform in lo..hi, units of 2^-32 sample per sample */
+  int32_t start;           /* DRAWN: integer part of T0, in samples */
+  uint32_t stream;         /* Philox counter word 3 */
+  uint64_t seed;
+  uint64_t frame_base;     /* index j of frame 0 of this call */
+} iq_fading_t;
+int iq_frames_fade(const float* x /*[n,len_in,2]*/, float* y /*[n,len_out,2]*/, int32_t* paths_out /*NULL or [n,8,33,2]*/,
+                   float* amps_out /*NULL or [n,8,33]*/, int64_t* clock_out /*NULL or [n,2]*/, int n_frames, int len_out,
+                   const iq_fading_t* par, iq_stream_t stream);
 /* Receiver for the frames above (csrc/receiver.hip): matched filter, one timing estimate per frame, one sample per symbol.
  * raw[n_frames, len, 2] fp32, x[n] = raw[n][0] + j raw[n][1], zero outside [0, len).  table G is DEVICE fp32 [n_frac][J+1],
  * J = sps * span, h = J / 2 (integer division): plain numbers to the kernel (receiver.py fills it with G[f][j] =

@@ -14,6 +14,8 @@ Import name: `vit_vs_raw_iq_amd` (the directory name contains hyphens; the repo-
   impairments -- channel impairments on the device (phase, frequency offset, shift, gain, AWGN): augmentation and accuracy curves
   synth     -- labelled synthetic frames made on the device as a keyed stream (FrameSynth, SynthStream, train_on_stream)
   waveform  -- pulse-shaped frames on the device: RRC shaping, true OQPSK, GMSK as CPM, timing phase, multipath (ShapedSynth)
+  fading    -- fading channel on the device: Doppler-spread taps (Clarke's model) and a sample-clock offset behind any raw frames
+               (Fading, FadedSynth, fading_curve)
   frontend  -- what the three image front ends below share (FrontEnd: checks, one autograd function, launch, fit, table cache)
                and front_end, the `spectrogram=` argument of the input paths
   spectrogram -- spectrogram front end on the device: (B, 2, len) frames -> the (B, 1, n_fft, width) image of the ViT, differentiable
@@ -49,6 +51,7 @@ from .adversarial import fgsm, pgd, robustness_curve, transfer_table
 from .impairments import Impairments, impair, impair_reference, impairment_curve
 from .synth import FrameSynth, SynthStream, synth_reference, train_on_stream
 from .waveform import ShapedSynth, gmsk_table, rrc_table, waveform_reference
+from .fading import FadedSynth, Fading, fading_curve, fading_reference, interp_table
 from .spectrogram import Spectrogram, spectrogram_reference, spectrogram_reference_bwd
 from .cyclic import CyclicSpectrum, cyclic_reference, cyclic_reference_bwd
 from .constellation import Constellation, constellation_reference, constellation_reference_bwd
@@ -72,4 +75,4 @@ __all__ = ["AMCTransformerViT", "AMCTransformerRawIQ", "EncoderViT", "EncoderRaw
            "carrier_reference_bwd", "dft_tables", "Equaliser", "equaliser_reference", "equaliser_reference_bwd",
            "LikelihoodClassifier", "likelihood_reference", "noise_for", "HybridLikelihoodClassifier",
            "likelihood_em_reference", "CumulantClassifier", "cumulants_reference", "cumulants_reference_bwd",
-           "cumulant_features_of", "FEATURE_NAMES"]
+           "cumulant_features_of", "FEATURE_NAMES", "Fading", "FadedSynth", "fading_curve", "fading_reference", "interp_table"]

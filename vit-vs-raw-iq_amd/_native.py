@@ -50,6 +50,15 @@ class Waveform(C.Structure):
                 ("tap_sigma", C.c_float * 8)]
 
 
+class Fading(C.Structure):
+    _fields_ = [("mode", C.c_int), ("len_in", C.c_int), ("n_taps", C.c_int), ("n_sin", C.c_int), ("K", C.c_int),
+                ("n_frac", C.c_int), ("normalise", C.c_int), ("timing", C.c_int), ("interp", C.c_void_p), ("snr_db", C.c_void_p),
+                ("paths", C.c_void_p), ("amps", C.c_void_p), ("clock", C.c_void_p), ("delay", C.c_int32 * 8),
+                ("los", C.c_float * 8), ("tap_sigma", C.c_float * 8), ("fd_lo", C.c_float), ("fd_hi", C.c_float),
+                ("d_lo", C.c_int32), ("d_hi", C.c_int32), ("start", C.c_int32), ("stream", C.c_uint32), ("seed", C.c_uint64),
+                ("frame_base", C.c_uint64)]
+
+
 class Receiver(C.Structure):
     _fields_ = [("sps", C.c_int), ("span", C.c_int), ("n_frac", C.c_int), ("mode", C.c_int), ("normalise", C.c_int),
                 ("table", C.c_void_p), ("u", C.c_void_p)]
@@ -178,6 +187,7 @@ SIGNATURES = {
     "iq_frames_impair": (_I, [_P, _P, _P, _I, _I, _I, C.POINTER(C.c_float), C.POINTER(Impair), _P]),
     "iq_frames_synth": (_I, [_P, _P, _P, _P, _P, _I, _I, C.POINTER(Synth), _P]),
     "iq_frames_waveform": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, C.POINTER(Waveform), _P]),
+    "iq_frames_fade": (_I, [_P, _P, _P, _P, _P, _I, _I, C.POINTER(Fading), _P]),
     "iq_frames_receive": (_I, [_P, _P, _P, _P, _I, _I, C.POINTER(Receiver), _P]),
     "iq_frames_receive_bwd": (_I, [_P, _P, _P, _P, _I, _I, C.POINTER(Receiver), _P]),
     "iq_frames_spectrogram": (_I, [_P, _P, _P, _I, _I, C.POINTER(Spectrogram), _P]),
