@@ -831,6 +831,74 @@ typedef struct iq_equaliser {
 int iq_frames_equalise(const float* x, float* out, float* w_out /*NULL or [n,L,2]*/, float* est /*NULL or [n,4]*/, int n_frames,
                        int len, const iq_equaliser_t* par, iq_stream_t stream);
 int iq_frames_equalise_bwd(const float* dout, float* dx, int n_frames, int len, const iq_equaliser_t* par, iq_stream_t stream);
+/* Tracking equaliser (csrc/equaliser_track.hip): the block CMA of iq_frames_equalise run per overlapping SEGMENT of the frame,
+ * every segment from the same start, and a filter whose weights move over the frame, interpolated between the segments' centres.
+ * It is for a channel that changes within a frame (iq_fading_t with a Doppler spread), which one filter per frame cannot follow.
+ * Frames, layouts (planar 0 / 1), L = taps in [1, 32], c = L / 2, z = 0 outside [0, len) and the four-fmaf-per-tap filter chain
+ * are those of iq_frames_equalise.
+ *   Segments.  seg in [1, 512] outputs each, hop in [1, seg] apart; len >= seg.  S = (len - seg) / hop + 1 (integer division)
+ *            segments, at most 256; segment j covers the outputs n = j hop + k, k = 0 .. seg-1.  (The outputs behind the last
+ *            segment, fewer than hop, belong to no segment; they are filtered with the last segment's weights.)
+ *   Taper.   h[k] = par->taper[k], DEVICE fp32 [seg], plain numbers shared by all frames and segments: the weight of output k
+ *            of a segment in that segment's cost.  The caller normalises it (sum 1: a mean); nothing is divided by seg.
+ *   IQ_EQT_CMA.  w_j^0 = par->w0[frame] (DEVICE fp32 [n_frames, L, 2]), or the unit spike at c when w0 is NULL: the same start for
+ *            every segment of the frame.  For t = 0 .. iters-1, with y[k] = sum_l w_j^t[l] z[j hop + k + c - l] (the filter chain;
+ *            the frame's samples outside the segment are read as they are):
+ *              d    = (fmaf(Im y, Im y, Re y * Re y)) - R
+ *              e[k] = ((Re y * d) * h[k], (Im y * d) * h[k])                 each product rounded
+ *              G[l] = sum_k conj(z[j hop + k + c - l]) e[k]:  Re += Re z Re e, then Im z Im e;  Im += Re z Im e, then - Im z Re e,
+ *                     all fmaf, as in iq_frames_equalise
+ *              w_j^{t+1}[l] = fmaf(-mu, G[l], w_j^t[l]), the real and the imaginary word alike
+ *            Every sum over k runs in one order: lane k % 64 its k ascending (a chain of fmaf from +0; at most 8 terms), then the
+ *            wave's butterfly (xor 32, 16, 8, 4, 2, 1).  One wave owns one (frame, segment).
+ *   Filter with weights over time.  For output n, t = n - seg / 2 (integer division): the offset from the first segment's centre.
+ *            t <= 0: w(n) = w_0.  t >= (S - 1) hop: w(n) = w_{S-1}.  Otherwise j = t / hop, r = t % hop, a = (float)r / (float)hop and
+ *            w(n)[l] = fmaf(a, w_{j+1}[l] - w_j[l], w_j[l]), every word alike (the difference rounded).  out[n] = sum_l w(n)[l]
+ *            z[n + c - l], the filter chain.  Equal neighbours interpolate to themselves exactly (a * 0 + w), so with iters = 0 out
+ *            has the bits of iq_frames_equalise under IQ_EQ_GIVEN with w = w0.
+ *   IQ_EQT_GIVEN.  w_j = par->w[frame, j] (DEVICE fp32 [n_frames, S, L, 2]); only the filter runs.  iters, mu, w0 and taper are
+ *            checked as below and not read otherwise; modulus is used by est[1].
+ * Outputs: out; w_out: fp32 [n_frames, S, L, 2] = the segments' weights (GIVEN: a copy of w).  Under IQ_EQT_CMA w_out is REQUIRED:
+ * the descent hands the weights to the filter through it, which is why no workspace is needed; under GIVEN it may be NULL.  est:
+ * NULL or fp32 [n_frames, 4] = {J of the frame filtered by w0 alone (NaN when GIVEN), J(out), max_j D_j with D_j = sum_l
+ * |w_j[l] - w0[l]|^2 (l ascending from +0, fmaf(dIm, dIm, fmaf(dRe, dRe, acc)), the differences rounded; the maximum walks j
+ * ascending and takes D_j where D_j > the best so far, so a NaN is neither larger nor beaten; NaN when GIVEN), (float)S}.
+ * J(y) = (sum_n d[n]^2) / (float)len over the whole frame, in the order of iq_frames_equalise (thread n % 256 ascending, fmaf(d, d,
+ * acc), the wave's butterfly, ((s0 + s1) + s2) + s3).  NaNs are not special-cased: they propagate within their frame only.  No
+ * atomics, no workspace, no allocation, no host synchronisation: two runs agree bit for bit and a frame's outputs depend on
+ * neither n_frames nor its position.  Two launches under CMA (the descent: one wave per (frame, segment), four per workgroup, a
+ * frame's segments neighbours in the grid, all iters steps inside the launch; then the filter: one workgroup per frame), one
+ * under GIVEN.
+ * iq_frames_equalise_track_bwd: the adjoint with the weights held fixed at par->w [n_frames, S, L, 2] (pass the forward's w_out)
+ * whatever par->mode says, interpolated as in the forward: dx[m] = sum_l conj(w(n)[l]) dout[n], n = m - c + l, dout = 0 outside the
+ * frame (w(n) for such an n is the first or the last segment's): a gather, per output one fmaf chain from +0 over l ascending,
+ * Re: + Re d Re w then + Im d Im w, Im: + Im d Re w then - Re d Im w.  One workgroup per frame.
+ * LDS: descent 4 x (two planes of 544 samples + 512 taper words) = 25.6 KB; filter and adjoint the frame as two planes with 32
+ * zeros on either side, the S x L weights, w0 and the sums: at most 133.4 KB.
+ * IQ_STATUS_ARG before any launch, outputs untouched: NULL x / out / dout / dx / par; taps < 1; len < 1; iters < 0; seg < 1;
+ * hop < 1 or hop > seg; len < seg; mu or modulus not finite, mu < 0; planar outside {0,1}; mode outside IQ_EQT_*; x / out / dout /
+ * dx not 8-byte (planar = 0) or 4-byte (planar = 1) aligned, any other pointer not 4-byte aligned; NULL w with IQ_EQT_GIVEN or in
+ * the backward; NULL taper or NULL w_out with IQ_EQT_CMA.  IQ_STATUS_UNSUPPORTED: taps > 32, iters > 4096, seg > 512, len * 8 bytes
+ * above 64 KB, more than 256 segments.  n_frames <= 0: success, nothing is launched. */
+enum { IQ_EQT_GIVEN = 0, IQ_EQT_CMA = 1 };
+typedef struct iq_equaliser_track {
+  int taps;       /* L in [1,32] */
+  int iters;      /* CMA steps per segment in [0,4096] */
+  int planar;     /* 0: x,out [n,len,2]; 1: [n,2,len] */
+  int mode;       /* IQ_EQT_* */
+  int seg;        /* outputs per segment in [1,512] */
+  int hop;        /* outputs between segment starts in [1,seg] */
+  float mu;       /* step size, >= 0 */
+  float modulus;  /* R */
+  const float* w;      /* DEVICE fp32 [n,S,L,2]: IQ_EQT_GIVEN and the backward */
+  const float* w0;     /* DEVICE fp32 [n,L,2] or NULL (the unit spike at c): IQ_EQT_CMA */
+  const float* taper;  /* DEVICE fp32 [seg]: IQ_EQT_CMA */
+} iq_equaliser_track_t;
+int iq_frames_equalise_track(const float* x, float* out, float* w_out /*[n,S,L,2]; NULL allowed when GIVEN*/,
+                             float* est /*NULL or [n,4]*/, int n_frames, int len, const iq_equaliser_track_t* par,
+                             iq_stream_t stream);
+int iq_frames_equalise_track_bwd(const float* dout, float* dx, int n_frames, int len, const iq_equaliser_track_t* par,
+                                 iq_stream_t stream);
 /* Likelihood classifier (csrc/likelihood.hip): the classical baseline of modulation classification.  For every frame and every
  * candidate constellation the log-likelihood of the frame's symbols as independent draws from the constellation in complex
  * Gaussian noise of known variance, over a table of carrier rotations (the phase is unknown), and the class of the largest.

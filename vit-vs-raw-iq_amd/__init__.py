@@ -27,6 +27,9 @@ Import name: `vit_vs_raw_iq_amd` (the directory name contains hyphens; the repo-
                differentiable (Carrier), and Synchronised, a front end behind it
   equaliser -- blind equaliser on the device: block constant-modulus descent of an L-tap filter per frame, differentiable
                (Equaliser); goes in front of the carrier recovery (Synchronised(equaliser=), ReceivedSynth(equaliser=, carrier=))
+  equaliser_track -- tracking equaliser on the device: the same descent per overlapping segment of the frame, from the block
+               solution, and a filter whose weights are interpolated over time (TrackingEqualiser, a subclass of Equaliser: goes
+               wherever that one goes); for channels that move within a frame (fading)
   likelihood -- likelihood classifier on the device: the classical AMC baseline over the candidate constellations and a table of
                carrier rotations (LikelihoodClassifier, noise_for); evaluation.evaluate_likelihood_with_confusion writes its report
   likelihood_em -- hybrid likelihood classifier on the device: the likelihood test with gain, phase and noise unknown, EM per frame
@@ -59,6 +62,8 @@ from .receiver import (Receiver, ReceivedSynth, mf_table, receiver_reference, re
                        transmitted_index)
 from .carrier import Carrier, Synchronised, carrier_reference, carrier_reference_bwd, dft_tables
 from .equaliser import Equaliser, equaliser_reference, equaliser_reference_bwd
+from .equaliser_track import (TrackingEqualiser, equaliser_track_reference, equaliser_track_reference_bwd, segment_step_reference,
+                              taper_table)
 from .likelihood import LikelihoodClassifier, likelihood_reference, noise_for
 from .likelihood_em import HybridLikelihoodClassifier, likelihood_em_reference
 from .cumulants import FEATURE_NAMES, CumulantClassifier, cumulant_features_of, cumulants_reference, cumulants_reference_bwd
@@ -75,4 +80,5 @@ __all__ = ["AMCTransformerViT", "AMCTransformerRawIQ", "EncoderViT", "EncoderRaw
            "carrier_reference_bwd", "dft_tables", "Equaliser", "equaliser_reference", "equaliser_reference_bwd",
            "LikelihoodClassifier", "likelihood_reference", "noise_for", "HybridLikelihoodClassifier",
            "likelihood_em_reference", "CumulantClassifier", "cumulants_reference", "cumulants_reference_bwd",
-           "cumulant_features_of", "FEATURE_NAMES", "Fading", "FadedSynth", "fading_curve", "fading_reference", "interp_table"]
+           "cumulant_features_of", "FEATURE_NAMES", "Fading", "FadedSynth", "fading_curve", "fading_reference", "interp_table",
+           "TrackingEqualiser", "equaliser_track_reference", "equaliser_track_reference_bwd", "segment_step_reference", "taper_table"]

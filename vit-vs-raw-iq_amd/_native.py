@@ -86,6 +86,11 @@ class Equaliser(C.Structure):
                 ("modulus", C.c_float), ("w", C.c_void_p), ("w0", C.c_void_p)]
 
 
+class EqualiserTrack(C.Structure):
+    _fields_ = [("taps", C.c_int), ("iters", C.c_int), ("planar", C.c_int), ("mode", C.c_int), ("seg", C.c_int), ("hop", C.c_int),
+                ("mu", C.c_float), ("modulus", C.c_float), ("w", C.c_void_p), ("w0", C.c_void_p), ("taper", C.c_void_p)]
+
+
 class Likelihood(C.Structure):
     _fields_ = [("points", C.c_void_p), ("classes", C.POINTER(SynthClass)), ("n_classes", C.c_int), ("rot", C.c_void_p),
                 ("n_rot", C.c_int), ("planar", C.c_int), ("mode", C.c_int), ("gain", C.c_void_p)]
@@ -200,6 +205,8 @@ SIGNATURES = {
     "iq_frames_carrier_bwd": (_I, [_P, _P, _I, _I, C.POINTER(Carrier), _P]),
     "iq_frames_equalise": (_I, [_P, _P, _P, _P, _I, _I, C.POINTER(Equaliser), _P]),
     "iq_frames_equalise_bwd": (_I, [_P, _P, _I, _I, C.POINTER(Equaliser), _P]),
+    "iq_frames_equalise_track": (_I, [_P, _P, _P, _P, _I, _I, C.POINTER(EqualiserTrack), _P]),
+    "iq_frames_equalise_track_bwd": (_I, [_P, _P, _I, _I, C.POINTER(EqualiserTrack), _P]),
     "iq_frames_likelihood": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, C.POINTER(Likelihood), _P]),
     "iq_frames_likelihood_em": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, C.POINTER(LikelihoodEm), _P]),
     "iq_frames_likelihood_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, C.POINTER(Likelihood), _P]),
